@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark: homomorphic AES-128 rounds on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-check]
-                    [--no-cpu-baseline] [--cpu-extended] [--no-configs] [--aes10-batch S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+                    [--full [--no-check] [--no-cpu-baseline] [--cpu-extended] [--no-configs]
+                            [--aes10-batch S] ...]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if
+--dump-outputs is given, and prints the result line; every other measurement and check below
+runs only with --full (where the options that switch single legs off keep their meaning).
 
 One *step* = one full middle AES-128 round (ShiftRows -> SubBytes -> MixColumns ->
 AddRoundKey) at N = 2^16, L = 30 over a batch of B ciphertext sets (8192 blocks each) per GPU.
@@ -13,11 +18,17 @@ rows x 8 +-1 bit ciphertexts carrying 8192 blocks, the columns in slot quarters 
 three rotations per bit; layout "bytes" (aes_xor_fhe.aes_round.AESRoundEngine): a set is one
 byte-major (hi, lo) Zeta-16 nibble pair carrying 2048 blocks.  Inputs (encrypted synthetic
 random AES states) and the encrypted round key are resident in HBM before the timed region.
-The timed steps run with kernel profiling OFF; a separate profiled pass afterwards gives the
-roofline figures.  Every output is decrypted and checked against FIPS-197 (outside the timed
-region) unless --no-check.
+The timed steps run with kernel profiling OFF; with --full a separate profiled pass afterwards
+gives the roofline figures, and every output is decrypted and checked against FIPS-197 (outside
+the timed region) unless --no-check.
 
-Also reported (rank 0, one JSON line):
+--dump-outputs DIR (rank 0, after the timed steps): the ciphertexts the last timed step returned,
+as DIR/<name>.npy in float64 (dump_outputs: a fixed, seeded sample of every ciphertext's residues
+and the decrypted slots of the sampled batch elements).  The engine then takes a fixed seed
+instead of one drawn from the OS, so the encrypted inputs -- and, the arithmetic being exact, the
+outputs -- are the same from run to run and two builds compare array for array.
+
+Also reported with --full (rank 0, one JSON line):
   aes128_10_rounds -- full AES-128 (ARK0 + 10 rounds, bit-mode bootstrapping) of --aes10-batch
                       sets per GPU (16 x 8192 = 131 072 blocks = BASELINE config 4's 64 x 2048);
   configs          -- BASELINE configs 2 (SubBytes via the reference-order
@@ -65,6 +76,10 @@ WORKLOAD = {
     "bytes": "nibble-domain Zeta-16 LUTs, byte-major SIMD packing",
 }
 SEED = 0x5EED5EED  # the CPU baseline's engine (reproducible); the GPU ranks share a 256-bit seed
+# --dump-outputs: the GPU ranks' 256-bit engine seed, and the seed and size of the output sample
+DUMP_ENGINE_SEED = 0x6A09E667F3BCC908BB67AE8584CAA73B3C6EF372FE94F82BA54FF53A5F1D36F1
+DUMP_SAMPLE_SEED = 0xD0E5
+DUMP_RESIDUE_BYTES = 32 << 20  # of the 64 MB a dump may take; the decrypted slots take <= 16 MB more
 
 PEAK_FP64_TFLOPS = 78.6  # MI355X vector FP64 (AMD spec: 256 CUs x 128 FLOP/clk x 2.4 GHz)
 PMC_FILE = ROOT / "profiles" / "r06" / "pmc" / "round_traffic.json"
@@ -272,6 +287,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the timed steps: the FIPS-197 check, the profiled "
+                         "(roofline) pass, the config / client-path / ten-round / config 5 legs, the "
+                         "scatter/gather leg under torchrun and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64, a fixed seeded "
+                         "sample); the engine then takes a fixed seed, so runs are comparable")
     ap.add_argument("--batch", type=int, default=32, help="ciphertext sets per GPU per step (8192 blocks each)")
     ap.add_argument("--layout", choices=("sliced", "rows", "bytes"), default="sliced",
                     help="sliced: columns as batch elements, ShiftRows a batch permutation "
@@ -322,7 +344,20 @@ def parse():
     ap.add_argument("--selftest-launch", action="store_true",
                     help="launcher self-test: every rank only joins the process group (gloo) and rank 0 "
                          "reports the world size; no GPU is touched")
-    return ap.parse_args()
+    return plain_unless_full(ap.parse_args())
+
+
+def plain_unless_full(args):
+    """Without --full, switch off every leg beside the timed steps: a plain run measures the
+    headline figure only."""
+    if not args.full:
+        args.check = False
+        args.profile_steps = 0
+        args.no_configs = args.no_harness = args.no_cpu_baseline = True
+        args.cpu_extended = False
+        args.client_batch = args.aes10_batch = 0
+        args.config5 = "off"
+    return args
 
 
 def _free_port():
@@ -432,8 +467,10 @@ def setup_engine(args, device, rank):
     from aes_xor_fhe.fhe import Engine
     from aes_xor_fhe.parallel import rank_nonce_start, shared_seed
     # one 256-bit engine key drawn on rank 0 and broadcast: every rank derives the same keys
+    # (--dump-outputs: a fixed one, so that the dumped outputs are the same from run to run)
     eng = Engine(log_n=args.log_n, max_level=args.max_level, special_primes=args.special_primes,
-                 scale_bits=args.scale_bits, device_id=device, seed=shared_seed(),
+                 scale_bits=args.scale_bits, device_id=device,
+                 seed=DUMP_ENGINE_SEED if args.dump_outputs else shared_seed(),
                  nonce_start=rank_nonce_start(rank), digit_primes=digit_primes(args))
     sk = eng.create_secret_key(1)
     pk = eng.create_public_key(sk)
@@ -598,6 +635,42 @@ def _materialize(out):
     contains all of its work."""
     from aes_xor_fhe.fhe import Engine
     Engine.materialize(out)
+
+
+def dump_outputs(eng, sk, cts, path):
+    """--dump-outputs: what the timed path returned, as float64 arrays under `path`.
+
+    cts are the output state's ciphertexts in order (RoundDriver.cts).  The whole state is tens of
+    GB, so a fixed sample (default_rng(DUMP_SAMPLE_SEED), the same for every run of one shape) is
+    kept: of every ciphertext one batch element, and of it
+      ciphertext_residues.npy  (ciphertexts, polynomials, limbs, sampled coefficients): the RNS
+                               residues (below 2^50, exact in float64) -- bit-identical between
+                               two builds that compute the same ciphertexts;
+      decrypted_slots.npy      (ciphertexts, 2, sampled slots): real and imaginary part of the
+                               decrypted slot values -- equal up to CKKS noise between builds
+                               whose ciphertexts differ but encrypt the same state."""
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    if max(eng.primes) >= 1 << 53:
+        raise ValueError("residues of this chain are not exact in float64")
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    n = 1 << eng.log_coeff_count
+    per_coeff = sum(c.npoly * (c.level + 1) for c in cts) * 8
+    coeff = np.sort(rng.choice(n, size=max(1, min(n, DUMP_RESIDUE_BYTES // per_coeff)), replace=False))
+    slots = np.sort(rng.choice(eng.slot_count, size=max(1, min(eng.slot_count, (16 << 20) // (len(cts) * 16))),
+                               replace=False))
+    res, dec = [], []
+    for c in cts:
+        one = eng.slice(c, int(rng.integers(c.batch)), 1)
+        res.append(eng.export_residues(one)[0][:, :, coeff].astype(np.float64))
+        v = np.asarray(eng.decrypt(one, sk)).reshape(-1)[slots]
+        dec.append(np.stack([v.real, v.imag]))
+    if len({r.shape for r in res}) == 1:
+        np.save(path / "ciphertext_residues.npy", np.stack(res))
+    else:  # ciphertexts at different levels: one array each
+        for i, r in enumerate(res):
+            np.save(path / f"ciphertext_residues_{i:02d}.npy", r)
+    np.save(path / "decrypted_slots.npy", np.stack(dec).astype(np.float64))
 
 
 def _timed(eng, fn, reps=1):
@@ -1008,6 +1081,9 @@ def main():
     if args.gpus < 1:
         log(f"--gpus {args.gpus}: need at least one")
         return 2
+    if args.steps < 1 or args.warmup < 0:
+        log(f"--steps {args.steps} --warmup {args.warmup}: need at least one timed step")
+        return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args)  # before anything imports torch or touches the GPU
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1096,6 +1172,9 @@ def main():
     log(f"timed: {args.steps} steps, {elapsed / args.steps * 1e3:.1f} ms/step")
     round_pool = eng.pool_stats()
     round_pool["held_over_peak_live"] = round(round_pool["held"] / max(round_pool["peak_live"], 1), 3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, R.keys[0], R.cts(out), args.dump_outputs)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     ok = None
     if args.check:
         ok = bool(np.array_equal(R.decrypt(out, args.batch), T.aes_round(blocks, rk)))
@@ -1127,7 +1206,8 @@ def main():
     gc.collect()
     eng.pool_trim()
 
-    log(f"checked ({ok}), profiled")
+    if args.full:
+        log(f"checked ({ok}), profiled")
 
     def secondary(name, fn):
         """A secondary leg: on one GPU its failure is reported in the line (the round above is
@@ -1146,7 +1226,7 @@ def main():
                 cur[0].pool_trim()
 
     sg = None
-    if dist is not None:
+    if dist is not None and args.full:
         sg = secondary("scatter/gather", lambda: scatter_gather_leg(args, eng, R, rank, world, barrier, allmax))
     configs = None
     log("scatter/gather done" if sg else "no scatter/gather leg")
@@ -1195,7 +1275,7 @@ def main():
         avg_launch_ms = ms_ntt.value / max(n_ntt.value, 1)
         achieved = by_ntt.value / (ms_ntt.value * 1e-3) / 1e9 if ms_ntt.value else 0.0
         alg_per_launch = by_ntt.value / max(n_ntt.value, 1)
-        pmc = pmc_record(args)
+        pmc = pmc_record(args) if args.full else None
         fam = (pmc or {}).get("ntt_family") or {}
         same_shape = bool(fam)
         rec = {
@@ -1206,6 +1286,7 @@ def main():
             "visible_devices": ndev,  # < n_gpus only in a rehearsal where ranks share a GPU (gloo)
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "weak",

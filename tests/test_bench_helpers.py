@@ -48,6 +48,85 @@ def test_committed_pmc_record_is_the_trees_own():
         assert per[cls]["hbm_bytes_per_launch"] > 0
 
 
+def test_plain_run_has_no_secondary_leg(monkeypatch):
+    """Without --full every leg beside the timed steps is off (check, profiled pass, configs,
+    harness, client path, ten rounds, config 5, CPU baseline); --full leaves the defaults and the
+    options that switch single legs off."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert not a.check and a.profile_steps == 0 and a.no_configs and a.no_harness and a.no_cpu_baseline
+    assert a.client_batch == 0 and a.aes10_batch == 0 and a.config5 == "off" and not a.cpu_extended
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-configs", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.check and a.profile_steps == 2 and a.no_configs and not a.no_harness
+    assert a.client_batch == 8 and a.aes10_batch == 16 and a.config5 == "auto" and not a.no_cpu_baseline
+    assert a.dump_outputs == "d"
+
+
+def test_dump_outputs_is_a_fixed_sample(oracle_lib, tmp_path):
+    """--dump-outputs: float64 arrays, the same for two engines of one seed; the residues are the
+    exported ones at the sampled batch element and coefficients, the slots the decrypted ones."""
+    import numpy as np
+    from aes_xor_fhe.fhe import Engine
+    dirs = []
+    for name in ("a", "b"):
+        e = Engine(_lib=oracle_lib, log_n=10, max_level=3, special_primes=2, seed=bench.DUMP_ENGINE_SEED)
+        sk = e.create_secret_key(1)
+        x = np.random.default_rng(3).standard_normal((3, e.slot_count))
+        cts = [e.encrypt(x, sk), e.encrypt(-2 * x, sk)]
+        bench.dump_outputs(e, sk, cts, tmp_path / name)
+        dirs.append(tmp_path / name)
+    files = sorted(p.name for p in dirs[0].iterdir())
+    assert files == ["ciphertext_residues.npy", "decrypted_slots.npy"]
+    for f in files:
+        a, b = np.load(dirs[0] / f), np.load(dirs[1] / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    res, dec = np.load(dirs[0] / files[0]), np.load(dirs[0] / files[1])
+    assert res.shape == (2, 2, 4, 1024) and dec.shape == (2, 2, e.slot_count)
+    # the sample of this shape: all 1024 coefficients and 512 slots fit; one batch element each
+    full = [e.export_residues(c) for c in cts]
+    for i in range(2):
+        hits = [b for b in range(3) if np.array_equal(full[i][b].astype(np.float64), res[i])]
+        assert len(hits) == 1
+        v = np.atleast_2d(e.decrypt(cts[i], sk))[hits[0]]
+        assert np.array_equal(dec[i], np.stack([v.real, v.imag]))
+        assert np.allclose(dec[i][0], (x if i == 0 else -2 * x)[hits[0]], atol=1e-3)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_dumps_its_outputs(product_lib, gpu_available, tmp_path):
+    """The benchmark itself, plain, at one slab of the default ring: --steps sets the timed steps,
+    the line holds ms_per_step and no secondary leg, and --dump-outputs leaves float64 arrays of at
+    most 64 MB whose decrypted slots are +-1 bits (a round's output state)."""
+    import subprocess
+
+    import numpy as np
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                        "--batch", "4", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=120, cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["warmup"] == 0 and rec["full"] is False
+    assert rec["unit"] == "blocks/s" and rec["higher_is_better"] is True and rec["dtype"] == "u64"
+    blocks = rec["config"]["blocks_per_gpu_per_step"]
+    assert blocks == 4 * 8192
+    assert rec["value"] == pytest.approx(blocks / (rec["ms_per_step"] * 1e-3), rel=1e-3)
+    assert rec["config"]["verified"] is None and rec["roofline"]["kernels"] is None
+    for leg in ("cpu_baseline", "aes128_10_rounds", "config5_shard", "configs", "client_path", "scatter_gather"):
+        assert rec[leg] is None, leg
+    files = sorted((tmp_path / "d").glob("*.npy"))
+    assert [f.name for f in files] == ["ciphertext_residues.npy", "decrypted_slots.npy"]
+    arrs = [np.load(f) for f in files]
+    assert all(a.dtype == np.float64 for a in arrs) and sum(a.nbytes for a in arrs) <= 64 << 20
+    res, dec = arrs
+    assert res.shape[:2] == (32, 2) and dec.shape == (32, 2, 32768)
+    assert np.array_equal(res, np.floor(res)) and res.min() >= 0 and res.max() < 2.0 ** 50
+    assert np.abs(np.abs(dec[:, 0]) - 1).max() < 0.05 and np.abs(dec[:, 1]).max() < 0.05
+
+
 class _FakeEngine:
     """engine_profile_kernels of two classes over 2 profiled steps: 'a' one dispatch per call,
     'b' three dispatches per call (as poly2_int's)."""
