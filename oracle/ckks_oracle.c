@@ -2050,6 +2050,7 @@ int aesfhe_power_basis(aesfhe_engine *e, const aesfhe_ct *c, int32_t d, const ae
 int aesfhe_lincomb(aesfhe_engine *e, const aesfhe_ct *const *cts, int32_t n, const double *re,
                    const double *im, aesfhe_ct **out) {
     if (n < 1) return fail(AESFHE_EARG, "empty linear combination");
+    if (n > 4096) return fail(AESFHE_EARG, "linear combination too long");  /* the HIP engine's bound */
     int l = cts[0]->level, B = 1, np = 2;
     for (int i = 0; i < n; i++) {
         if (cts[i]->level < l) l = cts[i]->level;
