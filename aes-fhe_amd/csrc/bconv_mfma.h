@@ -2,8 +2,8 @@
 //
 // A base conversion is a matrix product: out_t[k] = sum_i y_i[k] * H[i][t] mod p_t over the
 // source limbs i (y_i = [x_i * s_i]_{q_i}, canonical) and the targets t.  The exact-fp64 VALU
-// form (k_modup / k_moddown, kernels_ops.h) spends six fp64 ops per term and was issue-bound
-// (SQ WAIT_INST 0.69 / 0.74, fp64 at 0.34 / 0.38 of peak).  Here the sum runs exactly on
+// form (k_moddown, kernels_ops.h, and the ModUp kernel this one replaced) spends six fp64 ops per
+// term and was issue-bound (SQ WAIT_INST 0.69 / 0.74, fp64 at 0.34 / 0.38 of peak).  Here the sum runs exactly on
 // v_mfma_i32_32x32x32_i8 over byte planes:
 //   y_i = sum_a u_{i,a} 256^a (u the 8 bytes of the canonical u64), so
 //   sum_i y_i H[i][t] = sum_{(i,a)} u_{i,a} H'[(i,a)][t]  (mod p_t),  H' = 256^a H[i][t] mod p_t,

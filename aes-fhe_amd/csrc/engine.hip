@@ -172,7 +172,7 @@ struct aesfhe_engine {
     // the same for a fused ModDown's sources: N^{-1} (D/e_j)^{-1} / e_j, plain ([kMdrMaxE]) and
     // combined with r rescales ([cell][kMdrMaxE], as mdr_invf)
     double *md_ninvf = nullptr, *mdr_ninvf = nullptr;
-    TwD *mu_hatf, *md_phatf;  // base-conversion constants {w, w/q}
+    TwD* md_phatf;  // ModDown base-conversion constants {w, w/q} (k_moddown)
     // matrix-core base conversions (bconv_mfma.h): [set / cell][pid][8 planes][kBconvKT] signed
     // bytes, the XOR-0x80 corrections [set / cell][pid] and (2^32 mod p) / p per prime
     int8_t *bc_mu_tab = nullptr, *bc_md_tab = nullptr, *bc_mdr_tab = nullptr;
@@ -674,7 +674,6 @@ static void build_tables(aesfhe_engine* e) {
     const size_t mu_sets = (size_t)e->dnum * A;
     std::vector<u64> hhatinv(mu_sets * A, 0), hhat(mu_sets * A * np, 0);
     std::vector<double> hhatinvf(mu_sets * A, 0);
-    std::vector<TwD> hhatf(mu_sets * A * np, TwD{0, 0});
     for (int j = 0; j < e->dnum; j++)
         for (int a = 1; a <= A; a++) {
             int lo = j * A, hi = lo + a;
@@ -692,9 +691,6 @@ static void build_tables(aesfhe_engine* e) {
                     for (int i2 = lo; i2 < hi; i2++)
                         if (i2 != i) h = h_mulmod(h, Q[i2] % qt, qt);
                     hhat[(set * A + (i - lo)) * np + pid] = h;
-                    // [set][target pid][i]: a target's alpha constants are contiguous (one
-                    // scalar base, immediate offsets in k_modup)
-                    hhatf[(set * np + pid) * A + (i - lo)] = TwD{(double)h, (double)h / (double)qt};
                 }
             }
         }
@@ -712,7 +708,6 @@ static void build_tables(aesfhe_engine* e) {
         up(nh, &e->mu_nhatf);
     }
     up(hhat, &e->mu_hat);
-    up(hhatf, &e->mu_hatf);
     {  // matrix-core ModUp rows: [set][pid] (the digit's own pids are never targets)
         const size_t row = 8 * (size_t)kBconvKT;
         std::vector<int8_t> tab(mu_sets * np * row, 0);
@@ -967,7 +962,7 @@ static void engine_teardown(aesfhe_engine* e) {
     if (e->pool.trace) fclose(e->pool.trace);
     void* ptrs[] = {e->q, e->psi, e->ipsi, e->ninv, e->qinv, e->psif, e->ipsif, e->ninvf, e->rtwf, e->irtwf,
                     e->mu_hatinv, e->mu_hat, e->md_phatinv, e->md_phat, e->md_pinv, e->rs_inv,
-                    e->rs_mod, e->pmod, e->mu_hatinvf, e->mu_hatf, e->md_phatinvf, e->md_phatf,
+                    e->rs_mod, e->pmod, e->mu_hatinvf, e->md_phatinvf, e->md_phatf,
                     e->md_pinvf, e->rs_invf, e->ring_d, e->tw, e->itw, e->mdr_invf, e->mdr_hatf,
                     e->mdr_dinv, e->mdr_dinvf, e->pmodf, e->mdr_einv, e->mdr_dmodf, e->md_einv,
                     e->bc_mu_tab, e->bc_md_tab, e->bc_mdr_tab, e->bc_mu_corr, e->bc_md_corr, e->bc_mdr_corr,
@@ -2106,12 +2101,7 @@ extern "C" int aesfhe_dot_pt(aesfhe_engine* e, const aesfhe_ct* const* cts, cons
 // |eps| <= 1/2 per coefficient instead of the fast conversion's 0..K overflow.  r >= 1: combined ModDown + rescale -- P * addend joins the
 // accumulators in the inner product and one base conversion from E = {q_{l-r+1}..q_l, P} divides
 // by D = P q_l ... q_{l-r+1} (oracle/ckks_oracle.c moddown_r states the same procedure).
-// template launchers (a template argument list inside hipLaunchKernelGGL would split its macro args)
-template <int A, typename... Args>
-static void launch_modup(dim3 g, hipStream_t s, Args... args) {  // two coefficients per thread
-    g.x /= 2;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_modup<A, 2>), g, dim3(256), 0, s, args...);
-}
+// template launcher (a template argument list inside hipLaunchKernelGGL would split its macro args)
 template <int NE, typename... Args>
 static void launch_moddown(dim3 g, hipStream_t s, Args... args) {
     hipLaunchKernelGGL(k_moddown<NE>, g, dim3(256), 0, s, args...);
@@ -2128,13 +2118,9 @@ static unsigned bconv_groups(int N, int P, int ntarget) {
     return (unsigned)std::max(1L, std::min(g, (long)ntarget));
 }
 
-// Base conversions on the matrix cores (bconv_mfma.h), the default (round 5: ModUp 214 -> 190 us,
-// ModDown 453 -> 403 us per call, round +3.2 %, profiles/r05/ab/bconv_mfma/); AESFHE_BCONV_VALU=1
-// selects the exact-fp64 VALU kernels (k_modup / k_moddown) for A/B runs.  Same residues either way.
-static bool bconv_mfma_on() {
-    static const bool on = !(getenv("AESFHE_BCONV_VALU") && atoi(getenv("AESFHE_BCONV_VALU")));
-    return on;
-}
+// Base conversions run on the matrix cores (bconv_mfma.h; round 5: ModUp 214 -> 190 us, ModDown
+// 453 -> 403 us per call, round +3.2 %, profiles/r05/ab/bconv_mfma/).  The exact-fp64 VALU kernel
+// k_moddown serves only the ModDown sources too wide for them (K + r + 1 > 16 slots).
 // nslots = source slots (+ 1 for ModDown's v): ceil(nslots / 4) K-steps of 32 bytes (<= 4)
 static void launch_bconv(aesfhe_engine* e, BconvArgs a, int nz, int nslots, bool vc) {
     const int N = e->N, nstep = (nslots + 3) / 4, ntile = (a.nt + 3) / 4;
@@ -2160,20 +2146,99 @@ static void launch_bconv(aesfhe_engine* e, BconvArgs a, int nz, int nslots, bool
     HIPC(hipGetLastError());
 }
 
-// ModUp fused with the extension limbs' forward column pass (bconv_cols.h, N = 2^16; round 6,
-// VERDICT r5 item 1): the sources are y (the INTT folded qhat^{-1}), the extension limbs leave as
-// the column pass's raw-double intermediate.  AESFHE_MODUP_FUSED=0 selects k_bconv_mfma + the
-// column pass for A/B runs.  Same residues either way.
-static bool modup_fused_on() {
-    static const bool on = !(getenv("AESFHE_MODUP_FUSED") && !atoi(getenv("AESFHE_MODUP_FUSED")));
-    return on;
+// Base conversions fused with the targets' forward column pass (bconv_cols.h, N = 2^16; round 6,
+// VERDICT r5 item 1): the sources are y (the INTT before them folds qhat^{-1}), the targets leave
+// as the column pass's raw-double intermediate.  Elsewhere k_bconv_mfma and a separate column
+// pass run.  Same residues either way.
+static bool fused_bconv(const aesfhe_engine* e) { return e->logN == 16; }
+
+// ModUp of digit j at level l (its alpha limbs of the INTT copy dc, [B][l+1][N]) to every other
+// limb of Q_l u P, into dst ([B][l+1+K][N]).  ysrc: the sources are y = [x qhat^{-1}] already
+// (k_bconv_cols); otherwise the kernel multiplies by qhat^{-1} (k_bconv_mfma's sinvf).
+static BconvArgs modup_args(const aesfhe_engine* e, const u64* dc, int l, int j, u64* dst, bool ysrc) {
+    const int lo = j * e->A, alpha = std::min(lo + e->A, l + 1) - lo, ne = l + 1 + e->K;
+    const size_t set = (size_t)j * e->A + (alpha - 1);
+    BconvArgs a{};
+    a.src = dc + (long)lo * e->N;
+    a.sbs = (long)(l + 1) * e->N;
+    a.dst = dst;
+    a.dbs = (long)ne * e->N;
+    a.nc = 1;
+    a.ns = alpha;
+    a.s_nq = alpha;
+    a.s_q0 = lo;
+    a.sinvf = ysrc ? nullptr : e->mu_hatinvf + set * e->A;
+    a.nt = ne - alpha;
+    a.skip0 = lo;
+    a.skipn = alpha;
+    a.tl_l = l;
+    a.Lp1 = e->Lp1;
+    a.tab = e->bc_mu_tab + set * e->np * 8 * kBconvKT;
+    a.corr = e->bc_mu_corr + set * e->np;
+    a.pc = e->bc_pc;
+    a.qall = e->q;
+    a.qinvall = e->qinv;
+    return a;
 }
-// source row groups prefetched ahead (bconv_cols.h PF; AESFHE_BCC_PF=0 for A/B runs; PF 2 measured
-// slower and was dropped)
-static int bcc_pf() {
-    static const int pf = getenv("AESFHE_BCC_PF") ? std::max(0, std::min(1, atoi(getenv("AESFHE_BCC_PF")))) : 1;
-    return pf;
+
+// The tables of a ModDown by D = P q_l ... q_{l-r+1}: plain (r = 0) or combined with r rescales
+// (cell (r - 1, l) of the mdr_* tables, build_tables).
+struct MdTabs {
+    const double *invf, *ninvf, *einv;  // per source j: (D/e_j)^{-1} / e_j, the same times N^{-1}, 1 / e_j
+    const int8_t* tab;                  // matrix-core rows and corrections per target (bconv_mfma.h)
+    const double* corr;
+    const u64* dinv;                    // D^{-1} mod q_i per target, and as w / q for the finish
+    const double* dinvf;
+    const TwD* hatf;                    // k_moddown: (D/e_j) mod q_i, row stride hs; D mod q_i as w / q
+    int hs;
+    const double* dmodf;
+};
+static MdTabs md_tabs(const aesfhe_engine* e, int l, int r) {
+    if (r < 0 || r > kMdrMaxR || e->K + r > kMdrMaxE || l - r < 0) throw_err(AESFHE_EARG, "bad combined rescale depth %d", r);
+    if (!r)
+        return {e->md_phatinvf, e->md_ninvf, e->md_einv, e->bc_md_tab, e->bc_md_corr, e->md_pinv, e->md_pinvf,
+                e->md_phatf, e->K, e->pmodf};
+    const size_t cell = (size_t)(r - 1) * e->Lp1 + l, ce = cell * kMdrMaxE, cl = cell * e->Lp1;
+    return {e->mdr_invf + ce, e->mdr_ninvf + ce, e->mdr_einv + ce, e->bc_mdr_tab + cl * 8 * kBconvKT, e->bc_mdr_corr + cl,
+            e->mdr_dinv + cl, e->mdr_dinvf + cl, e->mdr_hatf + ce * e->Lp1, kMdrMaxE, e->mdr_dmodf + cl};
 }
+
+// ModDown of acc's dropped limbs (the top r Q limbs + P of both components; limb t at acc + t N,
+// batch / component strides abs_ / acs) to the l - r + 1 kept limbs, into dst ([B][2][l-r+1][N]).
+// ysrc: as modup_args (k_bconv_cols after an INTT that folded (D/e_j)^{-1}).
+static BconvArgs moddown_args(const aesfhe_engine* e, const MdTabs& t, const u64* acc, long abs_, long acs, int l, int r,
+                              u64* dst, bool ysrc) {
+    const int lk = l - r;
+    const long kN = (long)(lk + 1) * e->N;
+    BconvArgs a{};
+    a.src = acc + kN;
+    a.sbs = abs_;
+    a.scs = acs;
+    a.dst = dst;
+    a.dbs = 2 * kN;
+    a.dcs = kN;
+    a.nc = 2;
+    a.ns = e->K + r;
+    a.s_nq = r;
+    a.s_q0 = lk + 1;
+    a.s_p0 = e->Lp1;
+    a.sinvf = ysrc ? nullptr : t.invf;
+    a.einv = t.einv;
+    a.nt = lk + 1;
+    a.skip0 = lk + 1;
+    a.skipn = 0;
+    a.tl_l = lk;
+    a.Lp1 = e->Lp1;
+    a.tab = t.tab;
+    a.corr = t.corr;
+    a.pc = e->bc_pc;
+    a.qall = e->q;
+    a.qinvall = e->qinv;
+    return a;
+}
+
+// one source row group is prefetched ahead (bconv_cols.h PF = 1; PF 2 measured slower and was
+// dropped)
 template <bool VC>
 static void launch_bconv_cols_t(aesfhe_engine* e, const BconvArgs& a, int nz, int nslots) {
     const int nstep = (nslots + 3) / 4, ntile = (a.nt + 3) / 4;
@@ -2183,24 +2248,21 @@ static void launch_bconv_cols_t(aesfhe_engine* e, const BconvArgs& a, int nz, in
         throw_err(AESFHE_EUNSUPPORTED, "fused base conversion with a missing table");  // never launch on a null table
     const dim3 g((unsigned)(16 * nz * ntile));
     const Tabs T = e->tabs();
-    const int pf = bcc_pf();
-#define BCC(S, P) hipLaunchKernelGGL((k_bconv_cols<S, true, VC, P>), g, dim3(256), 0, e->stream, a, T, ntile)
-#define BCS(S) do { if (pf == 0) BCC(S, 0); else BCC(S, 1); } while (0)
+#define BCC(S) hipLaunchKernelGGL((k_bconv_cols<S, true, VC, 1>), g, dim3(256), 0, e->stream, a, T, ntile)
     switch (nstep) {
-        case 1: BCS(1); break;
-        case 2: BCS(2); break;
-        case 3: BCS(3); break;
-        default: BCS(4); break;
+        case 1: BCC(1); break;
+        case 2: BCC(2); break;
+        case 3: BCC(3); break;
+        default: BCC(4); break;
     }
-#undef BCS
 #undef BCC
     HIPC(hipGetLastError());
 }
 static void launch_bconv_cols(aesfhe_engine* e, const BconvArgs& a, int nz) { launch_bconv_cols_t<false>(e, a, nz, a.ns); }
 
 // The lazy-ModDown BSGS map with its babies formed inside the term sums (k_bsgs_terms) instead
-// of written (k_ks_inner_multi + k_dot_pt_ext_multi) is the default; AESFHE_BSGS_FUSED=0 selects
-// the unfused pair for A/B runs.  Its first form (one batch element per thread, every element
+// of written (k_ks_inner_multi + k_dot_pt_ext_multi) runs whenever only baby 0 is key-less; the
+// unfused pair serves the other plans.  Its first form (one batch element per thread, every element
 // re-reading its babies' keys) lost: 3.63 against 3.27 ms per refreshed bit ciphertext.  With
 // the key and plaintext words of each baby serving BB = 2..4 elements per thread it gains:
 // 3.15 against 3.23 ms, ten rounds 17.99 k / 17.89 k against 17.63 k / 17.66 k blocks/s
@@ -2215,18 +2277,6 @@ static std::vector<unsigned short> bsgs_block_order(int logN, const std::vector<
     if (!aesfhe::bsgs_block_order(logN, std::vector<uint64_t>(gal.begin(), gal.end()), ord))
         throw_err(AESFHE_EUNSUPPORTED, "bsgs block order is not a permutation");
     return ord;
-}
-
-static bool bsgs_fused_on() {
-    static const bool on = !(getenv("AESFHE_BSGS_FUSED") && !atoi(getenv("AESFHE_BSGS_FUSED")));
-    return on;
-}
-// The LDS-DMA pipelined key-switch row kernels (ks_fused.h k_nttf_rows_ks_p) are the default
-// (round 5: round +1.0 %, A/B/A/B on one box, profiles/r05/ab/ks_pipe/); AESFHE_KS_PIPE=0 selects
-// k_nttf_rows_ks for A/B runs
-static bool ks_pipe_on() {
-    static const bool on = !(getenv("AESFHE_KS_PIPE") && !atoi(getenv("AESFHE_KS_PIPE")));
-    return on;
 }
 
 static int ks_beta(const aesfhe_engine* e, int l) {
@@ -2245,7 +2295,7 @@ static void check_key_digits(aesfhe_engine* e, const aesfhe_key* k, int l) {
 // limb of Q_l u P outside the digit (the digit's own limbs are read from d by the inner product).
 // ext holds ks_beta(l) * B * (l+1+K) limbs.  Shared by every key in aesfhe_rotate_hoisted.
 // cols_only (fused_ntt engines): the extension limbs get only the NTT column pass; the row pass
-// runs inside k_nttf_rows_ks together with the inner product (ks_fused.h).
+// runs inside the key-switch row kernels together with the inner product (ks_fused.h).
 // pa, pb (fused_ntt engines): the input is poly 1 of each, multiplied (d2 = a1 b1 of a product)
 static void ks_modup(aesfhe_engine* e, const u64* d, long dbs, int B, int l, u64* ext, bool cols_only = false,
                      const Opnd* pa = nullptr, const Opnd* pb = nullptr, const u64* fac = nullptr) {
@@ -2257,7 +2307,7 @@ static void ks_modup(aesfhe_engine* e, const u64* d, long dbs, int B, int l, u64
     // column pass in one kernel (k_bconv_cols) from y = [x qhat^{-1}], which the INTT emits
     // directly (its N^{-1} times the digit's qhat^{-1} per limb; a one-limb digit's qhat^{-1} is 1,
     // so the spread path below reads the same words as before)
-    const bool fcols = e->logN == 16 && bconv_mfma_on() && modup_fused_on();
+    const bool fcols = fused_bconv(e);
     const double* lf = fcols ? e->mu_nhatf + (size_t)l * e->Lp1 : nullptr;
     // 1. INTT copy of the input
     Span sdc = span_s(dc.p, lN, l + 1, l + 1, 0, e->Lp1);
@@ -2276,19 +2326,17 @@ static void ks_modup(aesfhe_engine* e, const u64* d, long dbs, int B, int l, u64
     // pass reads it into ext_j -- the in-place pass read and wrote the same lines; one digit's
     // extension of extra memory, not one per digit (with the ModDown conv pass out of place as
     // well: round +0.8 %, A/B/A/B/A on one box, profiles/r04/ab/oop/)
-    const bool oop = cols_only;
-    std::unique_ptr<Tmp> mu;  // only when some digit runs k_modup (alpha > 1)
+    std::unique_ptr<Tmp> mu;  // only when some digit runs the unfused conversion (alpha > 1)
     bool any_wide = false;
     for (int j = 0; j < beta; j++) any_wide |= std::min((j + 1) * e->A, l + 1) - j * e->A > 1;
-    if (oop && any_wide && !fcols) mu.reset(new Tmp(e, (size_t)B * neN));
+    if (cols_only && any_wide && !fcols) mu.reset(new Tmp(e, (size_t)B * neN));
     for (int j = 0; j < beta; j++) {
         const int A = e->A, lo = j * A, hi = std::min(lo + A, l + 1), alpha = hi - lo;
-        const size_t set = (size_t)j * A + (alpha - 1);
         u64* exj = ext + (size_t)j * B * neN;
         u64* muj = mu ? mu->p : exj;  // where ModUp writes (mu absent: every digit is one limb)
         if (cols_only && alpha == 1) {
             // one-limb digit: the conversion is x mod p_t (hat = hatinv = 1), formed in the column
-            // pass's copy-in from the digit limb itself (no k_modup<1> write + read-back)
+            // pass's copy-in from the digit limb itself (no conversion launch, no write + read-back)
             const SpreadSrc ss{(const u64*)dc.p + (long)lo * N, lN, 0, 0, 0.0};
             auto kern = N == 65536 ? k_nttf_fwd_cols_spread<256, 3> : k_nttf_fwd_cols_spread<512, 3>;
             auto cols = [&](Span sp, int total) {
@@ -2302,25 +2350,7 @@ static void ks_modup(aesfhe_engine* e, const u64* d, long dbs, int B, int l, u64
         }
         if (fcols) {  // 2'. conversion + column pass in one launch, straight into ext_j (+ the row pass
                       // for callers that read the extension in NTT form: hoisted rotations, BSGS babies)
-            BconvArgs a{};
-            a.src = (const u64*)dc.p + (long)lo * N;
-            a.sbs = lN;
-            a.dst = exj;
-            a.dbs = neN;
-            a.nc = 1;
-            a.ns = alpha;
-            a.s_nq = alpha;
-            a.s_q0 = lo;
-            a.nt = ne - alpha;
-            a.skip0 = lo;
-            a.skipn = alpha;
-            a.tl_l = l;
-            a.Lp1 = e->Lp1;
-            a.tab = e->bc_mu_tab + set * e->np * 8 * kBconvKT;
-            a.corr = e->bc_mu_corr + set * e->np;
-            a.pc = e->bc_pc;
-            a.qall = e->q;
-            a.qinvall = e->qinv;
+            const BconvArgs a = modup_args(e, dc.p, l, j, exj, true);
             // algorithmic bytes: the digit's sources read once, the extension limbs written once
             {
                 ProfScope ps(e, FAM_KS, 8.0 * N * (double)B * ne, "modup_cols");
@@ -2341,35 +2371,8 @@ static void ks_modup(aesfhe_engine* e, const u64* d, long dbs, int B, int l, u64
         // 2. ModUp base conversion of digit j to every other limb, then NTT those limbs
         {
             ProfScope ps(e, FAM_KS, 8.0 * N * (double)B * ne, "modup");
-            if (alpha < 1 || alpha > 16) throw_err(AESFHE_EUNSUPPORTED, "ModUp digit width outside 1..16");
-            if (bconv_mfma_on()) {
-                BconvArgs a{};
-                a.src = (const u64*)dc.p + (long)lo * N;
-                a.sbs = lN;
-                a.dst = muj;
-                a.dbs = neN;
-                a.nc = 1;
-                a.ns = alpha;
-                a.s_nq = alpha;
-                a.s_q0 = lo;
-                a.sinvf = e->mu_hatinvf + set * A;
-                a.nt = ne - alpha;
-                a.skip0 = lo;
-                a.skipn = alpha;
-                a.tl_l = l;
-                a.Lp1 = e->Lp1;
-                a.tab = e->bc_mu_tab + set * e->np * 8 * kBconvKT;
-                a.corr = e->bc_mu_corr + set * e->np;
-                a.pc = e->bc_pc;
-                a.qall = e->q;
-                a.qinvall = e->qinv;
-                launch_bconv(e, a, B, alpha, false);
-            } else
-            AESFHE_DISPATCH16(alpha, launch_modup, dim3(N / 256, bconv_groups(N, B, ne), B), e->stream, (const u64*)dc.p, lN, muj, neN, lo, l, ne,
-                              (const double*)(e->mu_hatinvf + set * A), (const TwD*)(e->mu_hatf + set * A * e->np),
-                              A, e->q, e->qinv, e->Lp1, e->logN);
+            launch_bconv(e, modup_args(e, dc.p, l, j, muj, false), B, alpha, false);
         }
-        HIPC(hipGetLastError());
         auto fwd = [&](long off, int n, int nq, int p0, int total) {
             Span sp = span_s(exj + off, neN, n, nq, p0, e->Lp1);
             if (!cols_only) return ntt(e, sp, sp, total, false);
@@ -2389,30 +2392,24 @@ static void ks_modup(aesfhe_engine* e, const u64* d, long dbs, int B, int l, u64
 // acc instead of overwriting it (the lazy-ModDown sums of aesfhe_linear_bsgs).  ext_cols: ext
 // holds column-pass intermediates (ks_modup cols_only) and the inner product runs in the fused
 // row pass k_nttf_rows_ks.
-// pb (ext_cols, pmod, no accum): relinearisation of the product addend (x) pb (k_nttf_rows_ks
-// PROD; d unused).
 static void ks_inner_acc(aesfhe_engine* e, const u64* d, long dbs, const u64* ext, int B, int l,
-                         const aesfhe_key* k, Opnd addend, bool pmod, u64* acc, bool ext_cols, bool accum = false,
-                         const Opnd* pb = nullptr, const u64* fac = nullptr, const Opnd* pc = nullptr) {
+                         const aesfhe_key* k, Opnd addend, bool pmod, u64* acc, bool ext_cols, bool accum = false) {
     const int N = e->N, K = e->K, ne = l + 1 + K;
     const long neN = (long)ne * N;
     const int beta = ks_beta(e, l);
     check_key_digits(e, k, l);
     const double* pm = pmod ? (const double*)e->pmodf : (const double*)nullptr;
-    if (pb && (!ext_cols || !pmod || accum)) throw_err(AESFHE_EARG, "product key switch needs the fused combined path");
     if (ext_cols) {
         // row pass of every extension limb (credited half an NTT per limb: 8 N B) + the inner product
         // (key read once per call, accumulators written; ext never leaves the chip) + the Q-limb
-        // operands: the own digit's d limbs and the addend (PROD: a0, a1, b0, b1)
+        // operands: the own digit's d limbs and the addend
         const int nown = std::min(l + 1, beta * e->A);
-        const double opw = pb ? (4.0 + (pc && pc->ptr ? 2.0 : 0.0)) * (l + 1)
-                              : (double)nown + (pmod && addend.ptr ? (double)addend.np * (l + 1) : 0.0);
-        ProfScope ps(e, FAM_KS, 8.0 * N * ((double)B * (beta * ne - nown + opw) + (double)ne * (2.0 * beta + 2.0 * B * (accum ? 2 : 1))), pb ? "ks_rows_acc.prod" : "ks_rows_acc.ks");
+        const double opw = (double)nown + (pmod && addend.ptr ? (double)addend.np * (l + 1) : 0.0);
+        ProfScope ps(e, FAM_KS, 8.0 * N * ((double)B * (beta * ne - nown + opw) + (double)ne * (2.0 * beta + 2.0 * B * (accum ? 2 : 1))), "ks_rows_acc.ks");
         const int R = N / 256, blocks = 8 * B * (ne * (R / 8) / 8);
         const Opnd none{nullptr, 0, 0, 0};
-        auto kern = pb ? (R == 256 ? k_nttf_rows_ks<1, 256, true> : k_nttf_rows_ks<1, 512, true>)
-                       : (R == 256 ? k_nttf_rows_ks<1, 256, false> : k_nttf_rows_ks<1, 512, false>);
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, e->stream, d, dbs, ext, neN, (long)B * neN, (const u64*)k->d, 2L * e->np * N, (long)e->np * N, acc, 2 * neN, neN, B, beta, e->A, l, ne, e->tabs(), addend, pm, (int)accum, pb ? *pb : none, fac, pc ? *pc : none, 0, ne, KsFin{});
+        auto kern = R == 256 ? k_nttf_rows_ks<1, 256, false> : k_nttf_rows_ks<1, 512, false>;
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, e->stream, d, dbs, ext, neN, (long)B * neN, (const u64*)k->d, 2L * e->np * N, (long)e->np * N, acc, 2 * neN, neN, B, beta, e->A, l, ne, e->tabs(), addend, pm, (int)accum, none, (const u64*)nullptr, none, 0, ne, KsFin{});
     } else {
         ProfScope ps(e, FAM_KS, 8.0 * N * (double)ne * (beta * B + 2.0 * beta + 2.0 * B * (accum ? 2 : 1)), "ks_inner");
         auto inner = beta <= 4 ? k_ks_inner_all<4> : beta <= 8 ? k_ks_inner_all<8> : k_ks_inner_all<12>;
@@ -2421,28 +2418,19 @@ static void ks_inner_acc(aesfhe_engine* e, const u64* d, long dbs, const u64* ex
     HIPC(hipGetLastError());
 }
 
-// Key switch, second half, part 2: ModDown of acc (2 components, layout [B][2][l+1+K][N]; its
-// dropped limbs are overwritten) by D = P q_l ... q_{l-r+1} (fused with r rescales, DESIGN.md
-// 3.12) into o (level l - r) = (acc - conv) D^{-1} + fin_add.
-// ModDown, first part: INTT of acc's dropped limbs (top r Q limbs + the special limbs, layout
-// [B][2][l+1+K][N]) and their exact base conversion to the lk + 1 = l - r + 1 kept limbs, into conv
-// ([B][2][lk+1][N], coefficient form).  Returns D^{-1} mod q_i (as w / q) for the finish.
+// ModDown, first part: INTT of acc's dropped limbs (top r Q limbs + the special limbs; limb t at
+// acc + t N, batch / component strides abs_ / acs: the full [B][2][l+1+K][N] layout, or a block of
+// the dropped limbs alone with acc offset to match) and their exact base conversion to the
+// lk + 1 = l - r + 1 kept limbs, into conv ([B][2][lk+1][N], coefficient form).
 // rows_done (fused_ntt engines): the dropped limbs already hold their inverse row pass (raw
-// doubles, k_nttf_rows_ks EPI 2), so only the inverse column pass runs.
-// abs_ / acs: acc's batch and component strides (default: the full [B][2][l+1+K][N] layout; a
-// caller that holds only the dropped limbs passes its own, with acc offset so that limb t is at
-// acc + t N as before).
-static const double* moddown_conv(aesfhe_engine* e, u64* acc, int B, int l, int r, u64* conv, bool rows_done = false,
-                                  long abs_ = 0, long acs = 0) {
-    const int N = e->N, K = e->K, ne = l + 1 + K;
-    const long neN = (long)ne * N;
-    if (!acs) acs = neN, abs_ = 2 * neN;
-    if (r < 0 || r > kMdrMaxR || K + r > kMdrMaxE || l - r < 0) throw_err(AESFHE_EARG, "bad combined rescale depth %d", r);
-    const int lk = l - r;  // output level
+// doubles, k_nttf_rows_ks_p EPI 2), so only the inverse column pass runs.
+static void moddown_conv(aesfhe_engine* e, const MdTabs& t, u64* acc, long abs_, long acs, int B, int l, int r, u64* conv,
+                         bool rows_done) {
+    const int N = e->N, K = e->K, lk = l - r;
     const long kN = (long)(lk + 1) * N;
     // 4. ModDown: INTT the dropped limbs (top r Q limbs + the special limbs) of both accumulators
     {
-        Span ssp = span_s(acc + (long)(lk + 1) * N, acs, K + r, r, lk + 1, e->Lp1);
+        Span ssp = span_s(acc + kN, acs, K + r, r, lk + 1, e->Lp1);
         const int total = B * 2 * (K + r);
         if (rows_done) {
             ProfScope ps(e, FAM_NTT, 8.0 * N * (double)total, "ntt_inv_cols");
@@ -2453,68 +2441,30 @@ static const double* moddown_conv(aesfhe_engine* e, u64* acc, int B, int l, int 
             ntt(e, ssp, ssp, total, true);
         }
     }
-    const size_t cell = r ? (size_t)(r - 1) * e->Lp1 + l : 0;
-    const double* invf = r ? e->mdr_invf + cell * kMdrMaxE : e->md_phatinvf;
-    const TwD* hatf = r ? e->mdr_hatf + cell * kMdrMaxE * e->Lp1 : e->md_phatf;
-    const int hs = r ? kMdrMaxE : K;  // hatf row stride (sources of one target)
     {
         ProfScope ps(e, FAM_KS, 8.0 * N * (double)B * 2 * (K + r + lk + 1), "moddown");
         if (K + r < 1 || K + r > 16) throw_err(AESFHE_EUNSUPPORTED, "ModDown source width outside 1..16");
-        if (bconv_mfma_on() && K + r + 1 <= 16) {
-            BconvArgs a{};
-            a.src = acc + (long)(lk + 1) * N;
-            a.sbs = abs_;
-            a.scs = acs;
-            a.dst = conv;
-            a.dbs = 2 * kN;
-            a.dcs = kN;
-            a.nc = 2;
-            a.ns = K + r;
-            a.s_nq = r;
-            a.s_q0 = lk + 1;
-            a.s_p0 = e->Lp1;
-            a.sinvf = invf;
-            a.einv = r ? e->mdr_einv + cell * kMdrMaxE : e->md_einv;
-            a.nt = lk + 1;
-            a.skip0 = lk + 1;
-            a.skipn = 0;
-            a.tl_l = lk;
-            a.Lp1 = e->Lp1;
-            a.tab = r ? e->bc_mdr_tab + cell * e->Lp1 * 8 * kBconvKT : e->bc_md_tab;
-            a.corr = r ? e->bc_mdr_corr + cell * e->Lp1 : e->bc_md_corr;
-            a.pc = e->bc_pc;
-            a.qall = e->q;
-            a.qinvall = e->qinv;
-            launch_bconv(e, a, B * 2, K + r + 1, true);
-        } else
-        AESFHE_DISPATCH16(K + r, launch_moddown, dim3(N / 512, bconv_groups(N, B * 2, lk + 1), B * 2), e->stream, (const u64*)acc, abs_, acs, l, r, conv, 2 * kN, kN,
-                           invf, hatf, r ? e->mdr_einv + cell * kMdrMaxE : e->md_einv,
-                           r ? e->mdr_dmodf + cell * e->Lp1 : e->pmodf, e->Lp1, e->q, e->qinv, e->logN, hs);
+        if (K + r + 1 <= 16)
+            launch_bconv(e, moddown_args(e, t, acc, abs_, acs, l, r, conv, false), B * 2, K + r + 1, true);
+        else  // v has no slot left on the matrix cores: the exact-fp64 VALU kernel
+            AESFHE_DISPATCH16(K + r, launch_moddown, dim3(N / 512, bconv_groups(N, B * 2, lk + 1), B * 2), e->stream, (const u64*)acc, abs_, acs, l, r, conv, 2 * kN, kN,
+                              t.invf, t.hatf, t.einv, t.dmodf, e->Lp1, e->q, e->qinv, e->logN, t.hs);
     }
     HIPC(hipGetLastError());
-    return r ? e->mdr_dinvf + cell * e->Lp1 : e->md_pinvf;
 }
 
-// ModDown's conversion fused with conv's forward column pass (N = 2^16, rows_done accumulators;
-// bconv_cols.h VC): the inverse column pass of the dropped limbs scales them by N^{-1} (D/e_j)^{-1}
-// (md_ninvf / mdr_ninvf), so they leave as y_j, and k_bconv_cols writes conv's column-pass
-// intermediate straight into conv2 ([B][2][lk + 1][N], what the FIN row launch reads) -- conv's
-// coefficient form never reaches HBM.  Returns D^{-1} mod q_i (w / q) for the finish, as
-// moddown_conv.  Same residues as moddown_conv + ntt_fwd_cols.
-static bool moddown_cols_ok(const aesfhe_engine* e, int r) {
-    return e->logN == 16 && bconv_mfma_on() && modup_fused_on() && r >= 0 && r <= kMdrMaxR && e->K + r + 1 <= 16;
-}
-static const double* moddown_conv_cols(aesfhe_engine* e, u64* acc, int B, int l, int r, u64* conv2, long abs_, long acs,
-                                       bool rows_done = true) {
-    const int N = e->N, K = e->K;
-    const int lk = l - r;
-    const long kN = (long)(lk + 1) * N;
-    if (!moddown_cols_ok(e, r) || lk < 0) throw_err(AESFHE_EARG, "fused ModDown of depth %d", r);
-    const size_t cell = r ? (size_t)(r - 1) * e->Lp1 + l : 0;
+// ModDown's conversion fused with conv's forward column pass (N = 2^16; bconv_cols.h VC): the
+// inverse column pass of the dropped limbs scales them by N^{-1} (D/e_j)^{-1} (md_ninvf /
+// mdr_ninvf), so they leave as y_j, and k_bconv_cols writes conv's column-pass intermediate
+// straight into conv2 ([B][2][lk + 1][N], what the finishing row launch reads) -- conv's
+// coefficient form never reaches HBM.  Same residues as moddown_conv + ntt_fwd_cols.
+static bool moddown_cols_ok(const aesfhe_engine* e, int r) { return fused_bconv(e) && e->K + r + 1 <= 16; }
+static void moddown_conv_cols(aesfhe_engine* e, const MdTabs& t, u64* acc, long abs_, long acs, int B, int l, int r,
+                              u64* conv2, bool rows_done) {
+    const int N = e->N, K = e->K, lk = l - r;
     {
         Span ssp = span_s(acc + (long)(lk + 1) * N, acs, K + r, r, lk + 1, e->Lp1);
         const int total = B * 2 * (K + r);
-        const double* lf = r ? e->mdr_ninvf + cell * kMdrMaxE : e->md_ninvf;
         if (!rows_done) {  // canonical NTT-domain accumulators: the inverse row pass first
             ProfScope ps(e, FAM_NTT, 8.0 * N * (double)total, "ntt_inv_rows");
             hipLaunchKernelGGL((k_nttf_inv_rows<256, false>), dim3(16, total), dim3(256), 0, e->stream, ssp, ssp, e->tabs(),
@@ -2522,92 +2472,84 @@ static const double* moddown_conv_cols(aesfhe_engine* e, u64* acc, int B, int l,
             HIPC(hipGetLastError());
         }
         ProfScope ps(e, FAM_NTT, 8.0 * N * (double)total, "ntt_inv_cols");
-        hipLaunchKernelGGL((k_nttf_inv_cols<256, true>), dim3(16, total), dim3(256), 0, e->stream, ssp, e->tabs(), lf);
+        hipLaunchKernelGGL((k_nttf_inv_cols<256, true>), dim3(16, total), dim3(256), 0, e->stream, ssp, e->tabs(), t.ninvf);
         HIPC(hipGetLastError());
     }
-    BconvArgs a{};
-    a.src = acc + (long)(lk + 1) * N;
-    a.sbs = abs_;
-    a.scs = acs;
-    a.dst = conv2;
-    a.dbs = 2 * kN;
-    a.dcs = kN;
-    a.nc = 2;
-    a.ns = K + r;
-    a.s_nq = r;
-    a.s_q0 = lk + 1;
-    a.s_p0 = e->Lp1;
-    a.einv = r ? e->mdr_einv + cell * kMdrMaxE : e->md_einv;
-    a.nt = lk + 1;
-    a.skip0 = lk + 1;
-    a.skipn = 0;
-    a.tl_l = lk;
-    a.Lp1 = e->Lp1;
-    a.tab = r ? e->bc_mdr_tab + cell * e->Lp1 * 8 * kBconvKT : e->bc_md_tab;
-    a.corr = r ? e->bc_mdr_corr + cell * e->Lp1 : e->bc_md_corr;
-    a.pc = e->bc_pc;
-    a.qall = e->q;
-    a.qinvall = e->qinv;
-    {
-        // algorithmic bytes: the dropped limbs read once, conv's intermediate written once
-        ProfScope ps(e, FAM_KS, 8.0 * N * (double)B * 2 * (K + r + lk + 1), "moddown_cols");
-        launch_bconv_cols_t<true>(e, a, 2 * B, K + r + 1);
-    }
-    return r ? e->mdr_dinvf + cell * e->Lp1 : e->md_pinvf;
+    // algorithmic bytes: the dropped limbs read once, conv's intermediate written once
+    ProfScope ps(e, FAM_KS, 8.0 * N * (double)B * 2 * (K + r + lk + 1), "moddown_cols");
+    launch_bconv_cols_t<true>(e, moddown_args(e, t, acc, abs_, acs, l, r, conv2, true), 2 * B, K + r + 1);
 }
 
+// ModDown up to conv2 ([B][2][lk + 1][N]): the column-pass intermediate of conv that the finishing
+// row pass reads (fused_ntt engines) -- in one launch where moddown_cols_ok, else moddown_conv
+// and conv's column pass out of place (as ks_modup's).  converted() runs once the dropped limbs
+// are read: a caller that owns them releases them there, before conv2 is taken in the second
+// form.  `conv` of that form is read only by the column pass; it is the caller's to release.
+struct Conv2 {
+    std::unique_ptr<Tmp> conv, buf;  // released in reverse: buf, then conv
+};
+template <typename F>
+static Conv2 moddown_conv2(aesfhe_engine* e, const MdTabs& t, u64* acc, long abs_, long acs, int B, int l, int r,
+                           bool rows_done, F converted) {
+    const int lk = l - r, total = B * 2 * (lk + 1);
+    const long kN = (long)(lk + 1) * e->N;
+    Conv2 c;
+    if (moddown_cols_ok(e, r)) {
+        c.buf.reset(new Tmp(e, (size_t)B * 2 * kN));
+        moddown_conv_cols(e, t, acc, abs_, acs, B, l, r, c.buf->p, rows_done);
+        converted();
+        return c;
+    }
+    c.conv.reset(new Tmp(e, (size_t)B * 2 * kN));
+    moddown_conv(e, t, acc, abs_, acs, B, l, r, c.conv->p, rows_done);
+    converted();  // stream-ordered reuse of the dropped limbs from here on
+    c.buf.reset(new Tmp(e, (size_t)B * 2 * kN));
+    ProfScope ps(e, FAM_NTT, 8.0 * e->N * (double)total, "ntt_fwd_cols");
+    ntt_fwd_cols(e, span_s(c.conv->p, kN, lk + 1, lk + 1, 0, e->Lp1), span_s(c.buf->p, kN, lk + 1, lk + 1, 0, e->Lp1), total);
+    return c;
+}
+
+// Key switch, second half, part 2: ModDown of acc (2 components, layout [B][2][l+1+K][N]; its
+// dropped limbs are overwritten) by D = P q_l ... q_{l-r+1} (fused with r rescales, DESIGN.md
+// 3.12) into o (level l - r) = (acc - conv) D^{-1} + fin_add.
 static void moddown_acc(aesfhe_engine* e, u64* acc, int B, int l, int r, Opnd fin_add, aesfhe_ct* o) {
-    const int N = e->N, K = e->K, ne = l + 1 + K;
-    const long neN = (long)ne * N;
-    const int lk = l - r;  // output level
-    const long kN = (long)(lk + 1) * N;
-    if (moddown_cols_ok(e, r)) {  // conversion + conv's column pass fused, then the finishing row pass
-        Tmp conv2(e, (size_t)B * 2 * kN);
-        const double* dinvf = moddown_conv_cols(e, acc, B, l, r, conv2.p, 2 * neN, neN, false);
+    const int N = e->N, ne = l + 1 + e->K, lk = l - r;  // lk: output level
+    const long neN = (long)ne * N, kN = (long)(lk + 1) * N;
+    const MdTabs t = md_tabs(e, l, r);
+    if (fused_ntt(e)) {
+        // conv's NTT with the finish in the row pass's epilogue: conv never reaches HBM in NTT form
+        const Conv2 c = moddown_conv2(e, t, acc, 2 * neN, neN, B, l, r, false, [] {});
         const int total = B * 2 * (lk + 1);
         RowFin f{(const u64*)acc, 2 * neN, neN, Opnd2{fin_add.ptr, fin_add.bs, fin_add.ps, fin_add.np}, o->d,
-                 2L * (lk + 1) * N, (long)(lk + 1) * N, dinvf, lk + 1};
+                 2 * kN, kN, t.dinvf, lk + 1};
+        // the row pass (credited half an NTT) plus the finish: acc read, output written (+ addend)
         ProfScope ps(e, FAM_NTT, 8.0 * N * (double)total * (3.0 + (fin_add.ptr ? 1.0 : 0.0)), "ntt_fwd_rows_fin");
-        hipLaunchKernelGGL((k_nttf_fwd_rows_t<true, 256>), dim3(16, total), dim3(256), 0, e->stream,
-                           span_s(conv2.p, kN, lk + 1, lk + 1, 0, e->Lp1), e->tabs(), f);
+        auto kern = N == 65536 ? k_nttf_fwd_rows_t<true, 256> : k_nttf_fwd_rows_t<true, 512>;
+        hipLaunchKernelGGL(kern, dim3(N / 4096, total), dim3(256), 0, e->stream, span_s(c.buf->p, kN, lk + 1, lk + 1, 0, e->Lp1),
+                           e->tabs(), f);
         HIPC(hipGetLastError());
         return;
     }
     Tmp conv(e, (size_t)B * 2 * kN);
-    const double* dinvf = moddown_conv(e, acc, B, l, r, conv.p);
-    const size_t cell = r ? (size_t)(r - 1) * e->Lp1 + l : 0;
-    const u64* dinv = r ? e->mdr_dinv + cell * e->Lp1 : e->md_pinv;
+    moddown_conv(e, t, acc, 2 * neN, neN, B, l, r, conv.p, false);
     Span sc = span_s(conv.p, kN, lk + 1, lk + 1, 0, e->Lp1);
-    if (fused_ntt(e)) {
-        // conv NTT with the finish in the row pass's epilogue: conv never reaches HBM; the column
-        // pass out of place (as ks_modup's), into a second buffer the row pass reads
-        Tabs T = e->tabs();
-        const int total = B * 2 * (lk + 1);
-        Tmp conv2(e, (size_t)B * 2 * kN);
-        {
-            Span s2 = span_s(conv2.p, kN, lk + 1, lk + 1, 0, e->Lp1);
-            ProfScope ps(e, FAM_NTT, 8.0 * N * (double)total, "ntt_fwd_cols");
-            ntt_fwd_cols(e, sc, s2, total);
-            sc = s2;
-        }
-        RowFin f{(const u64*)acc, 2 * neN, neN, Opnd2{fin_add.ptr, fin_add.bs, fin_add.ps, fin_add.np}, o->d,
-                 2L * (lk + 1) * N, (long)(lk + 1) * N, dinvf, lk + 1};
-        // the row pass (credited half an NTT) plus the finish: acc read, output written (+ addend)
-        ProfScope ps(e, FAM_NTT, 8.0 * N * (double)total * (3.0 + (fin_add.ptr ? 1.0 : 0.0)), "ntt_fwd_rows_fin");
-        if (N == 65536) hipLaunchKernelGGL((k_nttf_fwd_rows_t<true, 256>), dim3(16, total), dim3(256), 0, e->stream, sc, T, f);
-        else hipLaunchKernelGGL((k_nttf_fwd_rows_t<true, 512>), dim3(32, total), dim3(256), 0, e->stream, sc, T, f);
-        HIPC(hipGetLastError());
-        return;
-    }
     ntt(e, sc, sc, B * 2 * (lk + 1), false);
     ProfScope psf(e, FAM_KS, 8.0 * N * (double)B * 2 * (lk + 1) * 4, "moddown_finish");
-    hipLaunchKernelGGL(k_moddown_finish, dim3(N / 256, lk + 1, B * 2), dim3(256), 0, e->stream, (const u64*)acc, 2 * neN, neN, (const u64*)conv.p, 2 * kN, kN, fin_add, out_of(o), e->q, dinv, dinvf, e->logN);
+    hipLaunchKernelGGL(k_moddown_finish, dim3(N / 256, lk + 1, B * 2), dim3(256), 0, e->stream, (const u64*)acc, 2 * neN, neN, (const u64*)conv.p, 2 * kN, kN, fin_add, out_of(o), e->q, t.dinv, t.dinvf, e->logN);
     HIPC(hipGetLastError());
 }
 
+// The pipelined key-switch row kernel (ks_fused.h; round 5: round +1.0 % over the unpipelined one,
+// A/B/A/B on one box, profiles/r05/ab/ks_pipe/) for a product (PROD) or a plain input, with the
+// finishing (EPI 1) or the inverse-row-pass (EPI 2) epilogue
+template <int R>
+static decltype(&k_nttf_rows_ks_p<R, false, 1>) ks_rows_kernel(bool prod, bool fin) {
+    return prod ? (fin ? k_nttf_rows_ks_p<R, true, 1> : k_nttf_rows_ks_p<R, true, 2>)
+                : (fin ? k_nttf_rows_ks_p<R, false, 1> : k_nttf_rows_ks_p<R, false, 2>);
+}
 
 // Key switch, second half, for fused_ntt engines (ext holds column-pass intermediates), with the
-// ModDown finish fused into the Q limbs' row pass: k_nttf_rows_ks runs twice --
+// ModDown finish fused into the Q limbs' row pass: k_nttf_rows_ks_p runs twice --
 //   1. the dropped limbs t = lk + 1 .. l + K (top r Q limbs + P) into acc, as ks_inner_acc;
 //   2. ModDown's INTT of those, the base conversion (conv) and conv's column pass (conv2);
 //   3. the kept limbs t = 0 .. lk (FIN): the inner product, conv's row pass and the finish
@@ -2617,7 +2559,7 @@ static void moddown_acc(aesfhe_engine* e, u64* acc, int B, int l, int r, Opnd fi
 // spends on them.  Residues identical: every step is exact mod q, outputs canonical.
 // pmod: P * addend joins the accumulators (combined ModDown + rescale, 3.12; the giants of
 // aesfhe_linear_bsgs with r = 0).  pb / fac / pc: the product relinearisation of keyswitch_prod
-// (k_nttf_rows_ks PROD).  acc_in / accum: add to the accumulators of earlier key switches in
+// (PROD).  acc_in / accum: add to the accumulators of earlier key switches in
 // acc_in (layout [B][2][l+1+K][N]; the last giant of aesfhe_linear_bsgs) instead of a fresh sum.
 static void ks_finish_fused(aesfhe_engine* e, const u64* d, long dbs, const u64* ext, int B, int l,
                             const aesfhe_key* k, Opnd addend, bool pmod, int r, Opnd fin_add, aesfhe_ct* o,
@@ -2626,13 +2568,14 @@ static void ks_finish_fused(aesfhe_engine* e, const u64* d, long dbs, const u64*
     const int N = e->N, K = e->K, ne = l + 1 + K, R = N / 256;
     const long neN = (long)ne * N;
     const int beta = ks_beta(e, l), lk = l - r;
+    const bool had_own = acc_in == nullptr;  // the accumulators are a block of this call's own
     check_key_digits(e, k, l);
-    if (r < 0 || r > kMdrMaxR || K + r > kMdrMaxE || lk < 0) throw_err(AESFHE_EARG, "bad combined rescale depth %d", r);
+    const MdTabs t = md_tabs(e, l, r);
     if (pb && r < 1) throw_err(AESFHE_EARG, "product key switch needs the fused combined path");
+    if (accum && (had_own || pb)) throw_err(AESFHE_EARG, "accumulating key switch without accumulators");
     const long kN = (long)(lk + 1) * N;
     const double* pm = pmod ? (const double*)e->pmodf : (const double*)nullptr;
     const Opnd none{nullptr, 0, 0, 0};
-    if (accum && (!acc_in || pb)) throw_err(AESFHE_EARG, "accumulating key switch without accumulators");
     // bytes of a launch over limbs [t0, t0 + nt), nq of them Q limbs: ext rows (every digit but
     // the limb's own), the own digit's d rows and the addend (PROD: a0, a1, b0, b1 [, c0, c1]),
     // the key words, and the outputs (acc: 2 B nt limbs; FIN: conv read + out written, + fin_add)
@@ -2651,15 +2594,7 @@ static void ks_finish_fused(aesfhe_engine* e, const u64* d, long dbs, const u64*
         ProfScope ps(e, FAM_KS, bytes(nt, nq, fin),
                      fin ? (pb ? "ks_rows_fin.prod" : "ks_rows_fin.ks") : (pb ? "ks_rows_inner.prod" : "ks_rows_inner.ks"));
         // the dropped limbs leave with their inverse row pass done (EPI 2), the kept ones finished (EPI 1)
-        auto kern = R == 256 ? (pb ? (fin ? k_nttf_rows_ks<1, 256, true, 1> : k_nttf_rows_ks<1, 256, true, 2>)
-                                   : (fin ? k_nttf_rows_ks<1, 256, false, 1> : k_nttf_rows_ks<1, 256, false, 2>))
-                             : (pb ? (fin ? k_nttf_rows_ks<1, 512, true, 1> : k_nttf_rows_ks<1, 512, true, 2>)
-                                   : (fin ? k_nttf_rows_ks<1, 512, false, 1> : k_nttf_rows_ks<1, 512, false, 2>));
-        if (ks_pipe_on())
-            kern = R == 256 ? (pb ? (fin ? k_nttf_rows_ks_p<256, true, 1> : k_nttf_rows_ks_p<256, true, 2>)
-                                  : (fin ? k_nttf_rows_ks_p<256, false, 1> : k_nttf_rows_ks_p<256, false, 2>))
-                            : (pb ? (fin ? k_nttf_rows_ks_p<512, true, 1> : k_nttf_rows_ks_p<512, true, 2>)
-                                  : (fin ? k_nttf_rows_ks_p<512, false, 1> : k_nttf_rows_ks_p<512, false, 2>));
+        auto kern = R == 256 ? ks_rows_kernel<256>(pb != nullptr, fin) : ks_rows_kernel<512>(pb != nullptr, fin);
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, e->stream, d, dbs, ext, neN, (long)B * neN, (const u64*)k->d,
                            2L * e->np * N, (long)e->np * N, acc, abs_, acs, B, beta, e->A, l, ne, e->tabs(), addend, pm,
                            (int)accum, pb ? *pb : none, fac, pc ? *pc : none, t0, nt, kf);
@@ -2668,40 +2603,23 @@ static void ks_finish_fused(aesfhe_engine* e, const u64* d, long dbs, const u64*
     // only the dropped limbs lk + 1 .. ne - 1 are written: an own accumulator holds just those
     // ([B][2][nd][N], nd = ne - lk - 1; ADVICE r4: the full [B][2][ne][N] block was ~1 GB per key
     // switch at B = 32, l = 30 of memory never touched), addressed through a base pointer offset by
-    // lk + 1 limbs so that limb t still sits at acc + t N; the FIN launch does not read acc then
+    // lk + 1 limbs so that limb t still sits at acc + t N
     const int nd = ne - (lk + 1);
     std::unique_ptr<Tmp> own;
-    if (!acc_in) own.reset(new Tmp(e, (size_t)B * 2 * nd * N));
+    if (had_own) own.reset(new Tmp(e, (size_t)B * 2 * nd * N));
     // (an address, not a C++ pointer into the block: only limbs >= lk + 1 are ever formed from it,
-    // by the dropped limbs' launch and moddown_conv; the FIN launch gets no accumulators at all)
+    // by the dropped limbs' launch and the ModDown conversion)
     u64* acc = acc_in ? acc_in : reinterpret_cast<u64*>(reinterpret_cast<uintptr_t>(own->p) - (uintptr_t)(lk + 1) * N * sizeof(u64));
     const long abs_ = acc_in ? 2 * neN : 2L * nd * N, acs = acc_in ? neN : (long)nd * N;
     launch(lk + 1, nd, false, acc, abs_, acs, KsFin{});
-    const double* dinvf;
-    std::unique_ptr<Tmp> conv2;
-    if (moddown_cols_ok(e, r)) {  // conversion + conv's column pass in one launch (bconv_cols.h)
-        conv2.reset(new Tmp(e, (size_t)B * 2 * kN));
-        dinvf = moddown_conv_cols(e, acc, B, l, r, conv2->p, abs_, acs);
-        if (own) own.reset();
-    } else {
-        std::unique_ptr<Tmp> conv(new Tmp(e, (size_t)B * 2 * kN));
-        dinvf = moddown_conv(e, acc, B, l, r, conv->p, true, abs_, acs);
-        if (own) own.reset();  // the dropped limbs are converted: stream-ordered reuse from here on
-        conv2.reset(new Tmp(e, (size_t)B * 2 * kN));
-        {
-            const int total = B * 2 * (lk + 1);
-            ProfScope ps(e, FAM_NTT, 8.0 * N * (double)total, "ntt_fwd_cols");
-            ntt_fwd_cols(e, span_s(conv->p, kN, lk + 1, lk + 1, 0, e->Lp1), span_s(conv2->p, kN, lk + 1, lk + 1, 0, e->Lp1), total);
-        }
-        conv.reset();  // conv's coefficient form is read only by the column pass
-    }
+    // the own block goes back once the dropped limbs are converted
+    Conv2 c = moddown_conv2(e, t, acc, abs_, acs, B, l, r, true, [&] { own.reset(); });
+    c.conv.reset();
     HIPC(hipGetLastError());
-    const KsFin kf{conv2->p, 2 * kN, kN, o->d, 2L * (lk + 1) * N, (long)(lk + 1) * N, dinvf,
-                   Opnd2{fin_add.ptr, fin_add.bs, fin_add.ps, fin_add.np}};
-    // the kept limbs' accumulators exist only in acc_in (accumulating giants); with an own block
-    // FIN reads none: nullptr, so that no later change can read conv2's reuse of that memory
-    if (own && accum) throw_err(AESFHE_EARG, "accumulating key switch without accumulators");
-    launch(0, lk + 1, true, own ? nullptr : acc, abs_, acs, kf);
+    const KsFin kf{c.buf->p, 2 * kN, kN, o->d, 2 * kN, kN, t.dinvf, Opnd2{fin_add.ptr, fin_add.bs, fin_add.ps, fin_add.np}};
+    // the kept limbs' accumulators exist only in acc_in (accumulating giants, read with accum);
+    // with an own block -- released above, its memory perhaps conv2's by now -- FIN gets nullptr
+    launch(0, lk + 1, true, had_own ? nullptr : acc, abs_, acs, kf);
 }
 
 // Key switch, second half: inner product of ext (ks_modup of d) with key k, ModDown (fused with
@@ -2727,7 +2645,7 @@ static void keyswitch(aesfhe_engine* e, const u64* d, long dbs, int B, int l, co
 
 // relinearisation + r >= 1 rescales of the product a (x) b without a tensor ciphertext
 // (fused_ntt engines, combined ModDown + rescale): d2 = a1 b1 is formed in the INTT's copy-in,
-// d0, d1 and the own digit's d2 term in the prologue of k_nttf_rows_ks (PROD).  Same residues
+// d0, d1 and the own digit's d2 term in the prologue of k_nttf_rows_ks_p (PROD).  Same residues
 // as tensor_ct + relin_rescale; the 3-polynomial tensor (3 limbs written, 3 read back, per
 // Q limb) never reaches HBM.
 // fac / pc (optional): the multiply-add of aesfhe_mul_fma, per-prime {alpha, C, K} (device) and
@@ -3008,11 +2926,10 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
     std::vector<std::unique_ptr<Tmp>> E;
     bool any_key = false;
     for (int i = 0; i < nb; i++) any_key |= bkeys[i] != nullptr;
-    // fused (AESFHE_BSGS_FUSED=1, bsgs_fused_on): the babies are formed inside the term sums
-    // (k_bsgs_terms) from the extension and the keys, never written
-    bool only_first_keyless = true;  // k_bsgs_terms peels a key-less (identity) baby at index 0 only
-    for (int i = 1; i < nb; i++) only_first_keyless &= bkeys[i] != nullptr;
-    const bool fused_terms = bsgs_fused_on() && only_first_keyless;
+    // fused: the babies are formed inside the term sums (k_bsgs_terms) from the extension and the
+    // keys, never written
+    bool fused_terms = true;  // k_bsgs_terms peels a key-less (identity) baby at index 0 only
+    for (int i = 1; i < nb; i++) fused_terms &= bkeys[i] != nullptr;
     std::unique_ptr<Tmp> ext_keep;
     if (fused_terms && any_key) {
         ext_keep.reset(new Tmp(e, (size_t)ks_beta(e, l) * B * neN));

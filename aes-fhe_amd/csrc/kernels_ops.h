@@ -344,66 +344,6 @@ __global__ void k_rescale_finish_g(const u64* __restrict__ c, long cps, const u6
     outs[g][(long)rem * ops + ((long)i << logN) + k] = mul_w(sub_m(cv, tv, q), inv[i], invf[i], q);
 }
 
-// ModUp base conversion of digit [lo, lo+alpha) (INTT'ed limbs of dc) to the other limbs t of
-// the extended basis (Q_l then P), exact fp64 arithmetic (kernels.h fmul_rem):
-//   y_i = [x_i * qhat_i^{-1}]_{q_i} in [0, q_i) (canonical, so the multiple of Q that the fast
-//   conversion adds is the oracle's), ext[t] = sum_i y_i * (qhat_i mod p_t) mod p_t.
-// Constants: hatinv as w/q (w = rint(wq * q) is exact), hat as {w, w/q}, [target pid][i] with
-// row stride hs.  grid (N/256,
-// ceil(ne/16), B): each thread converts one coefficient into up to 16 target limbs.
-// A = alpha (digit width) as a template parameter: the per-target constant loads are then
-// unconditional and the compiler issues all A of them before the first use (with a runtime
-// alpha every term was a branch, and each scalar load was waited for on its own).
-template <int A, int C>  // C coefficients per thread (k + 256 c): every constant fetched serves C
-__global__ void k_modup(const u64* __restrict__ dc, long dcs, u64* __restrict__ ext, long exs,
-                        int lo, int l, int ne, const double* __restrict__ hatinvf,
-                        const TwD* __restrict__ hat, int hs, const u64* __restrict__ qall,
-                        const double* __restrict__ qinvall, int Lp1, int logN) {
-    const int k = blockIdx.x * (256 * C) + threadIdx.x;
-    const int bb = blockIdx.z;
-    double y[C][A];
-#pragma unroll
-    for (int i = 0; i < A; i++) {
-        const int pi = lo + i;
-        const double qp = (double)qall[pi];
-        const double f = hatinvf[i], w = tw_w(f, qp);
-        const u64* src = dc + (long)bb * dcs + ((long)pi << logN) + k;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            const double r = fmul_rem(u2d(src[256 * c]), w, f, qp);
-            y[c][i] = r < 0.0 ? r + qp : r;
-        }
-    }
-    const int tg = (ne + gridDim.y - 1) / gridDim.y, t0 = blockIdx.y * tg;  // targets per thread
-    for (int t = t0; t < t0 + tg && t < ne; t++) {
-        if (t >= lo && t < lo + A) continue;
-        const int pid = t <= l ? t : Lp1 + (t - l - 1);
-        const double qt = (double)qall[pid], qti = qinvall[pid];
-        TwD f[A];
-#pragma unroll
-        for (int i = 0; i < A; i++) f[i] = hat[pid * hs + i];  // [target][source]: contiguous
-        double acc[C];
-#pragma unroll
-        for (int c = 0; c < C; c++) acc[c] = 0.0;
-        // terms lie in (-1.5 qt, 1.5 qt): below 2^42 the A <= 16 of them sum exactly without
-        // folding; 50-bit targets fold every 4 (uniform branch)
-        const bool fold = qt >= kBigPrime;
-#pragma unroll
-        for (int i = 0; i < A; i++) {
-#pragma unroll
-            for (int c = 0; c < C; c++) acc[c] += fmul_rem_r(y[c][i], f[i].w, f[i].wq, qt);
-            if (fold && (i & 3) == 3) {
-#pragma unroll
-                for (int c = 0; c < C; c++) acc[c] = fred(acc[c], qt, qti);
-            }
-        }
-        u64* o = ext + (long)bb * exs + ((long)t << logN) + k;
-        // streaming stores: ext of one digit (B ne limbs) is far larger than the caches
-#pragma unroll
-        for (int c = 0; c < C; c++) __builtin_nontemporal_store(fcanon(acc[c], qt, qti), &o[256 * c]);
-    }
-}
-
 // All digits at once: acc[b][c][t] = sum_j e_j[b][t] * key_j,c[pid(t)], e_j = d (limbs of digit
 // j, NTT) or ext_j (other limbs).  key layout [dnum][2][np][N]; ext layout [beta][B][ne][N].
 // grid (N/256, ne, 1); loops over the batch so each key word is read once per batch.
@@ -547,7 +487,11 @@ __global__ void k_ks_inner_multi(const u64* __restrict__ d, long dbs, const u64*
 // multiples of D in sum_j y_j (D/e_j), and conv[i] -= v * (D mod q_i), so the division rounds to
 // nearest like a plain rescale (einv[j] = 1/e_j, dmodf[i] = (D mod q_i)/q_i).
 // invf[j]: w/q table, hat[i * hs + j]: {w, w/q}.  grid (N/256, ceil((l-r+1)/16), B*2)
-// NE = K + r (dropped limbs) as a template parameter, for the same reason as k_modup's A.
+// Exact fp64 arithmetic (kernels.h fmul_rem); ModUp and the narrower ModDowns run on the matrix
+// cores (bconv_mfma.h), this kernel where K + r + 1 > 16 leaves v no slot there.
+// NE = K + r (dropped limbs) as a template parameter: the per-target constant loads are then
+// unconditional and the compiler issues all NE of them before the first use (with a runtime
+// count every term was a branch, and each scalar load was waited for on its own).
 template <int NE>
 __global__ void k_moddown(const u64* __restrict__ acc, long abs_, long acs, int l, int r,
                           u64* __restrict__ conv, long cbs, long ccs,
@@ -555,7 +499,7 @@ __global__ void k_moddown(const u64* __restrict__ acc, long abs_, long acs, int 
                           const double* __restrict__ einv, const double* __restrict__ dmodf,
                           int Lp1, const u64* __restrict__ qall, const double* __restrict__ qinvall,
                           int logN, int hs) {
-    // two coefficients per thread (k, k + 256), as k_modup
+    // two coefficients per thread (k, k + 256): every constant fetched serves both
     const int k = blockIdx.x * 512 + threadIdx.x;
     const int bb = blockIdx.z >> 1, c = blockIdx.z & 1;
     const u64* src = acc + (long)bb * abs_ + (long)c * acs;
@@ -590,7 +534,7 @@ __global__ void k_moddown(const u64* __restrict__ acc, long abs_, long acs, int 
 #pragma unroll
         for (int j = 0; j < NE; j++) f[j] = hat[i * hs + j];  // [target][source]: contiguous
         double sum = fmul_rem(-v, wd, fd, q), sum2 = fmul_rem(-v2, wd, fd, q);
-        const bool fold = q >= kBigPrime;  // as k_modup: small targets sum NE + 1 terms unfolded
+        const bool fold = q >= kBigPrime;  // small targets (terms in (-1.5 q, 1.5 q)) sum NE + 1 terms unfolded
 #pragma unroll
         for (int j = 0; j < NE; j++) {
             sum += fmul_rem_r(y[j], f[j].w, f[j].wq, q);
@@ -601,7 +545,7 @@ __global__ void k_moddown(const u64* __restrict__ acc, long abs_, long acs, int 
             }
         }
         u64* o = conv + (long)bb * cbs + (long)c * ccs + ((long)i << logN) + k;
-        __builtin_nontemporal_store(fcanon(sum, q, qi), &o[0]);  // streaming, as k_modup
+        __builtin_nontemporal_store(fcanon(sum, q, qi), &o[0]);  // streaming: conv is far larger than the caches
         __builtin_nontemporal_store(fcanon(sum2, q, qi), &o[256]);
     }
 }

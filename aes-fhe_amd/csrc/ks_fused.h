@@ -6,8 +6,16 @@
 // switch.  Here ks_modup stops after the column pass (the raw-double intermediate stays in the
 // ext buffer) and one workgroup per (target limb t, 8-row block, batch element b) runs the row
 // pass of ext[j][b][t] for every digit j in registers, multiplies by the key digit and
-// accumulates, writing only the two accumulators acc[b][0/1][t] (accum: added to what acc holds)
-// -- the same canonical values k_ks_inner_all produces (the arithmetic is exact mod q; only the lazy ranges differ).
+// accumulates -- the same canonical values k_ks_inner_all produces (the arithmetic is exact mod q;
+// only the lazy ranges differ).  Two kernels:
+//   k_nttf_rows_ks    unpipelined, every limb of Q_l u P: writes the two accumulators
+//                     acc[b][0/1][t] canonical (accum: added to what acc holds) -- the accumulating
+//                     giants of aesfhe_linear_bsgs (engine.hip ks_inner_acc).
+//   k_nttf_rows_ks_p  pipelined (LDS-DMA of the next digit's row), a range of limbs, plain or PROD
+//                     (the relinearisation of a product, formed in the prologue), with one of two
+//                     epilogues: INV, the accumulators' inverse row pass into acc (ModDown's dropped
+//                     limbs), or FIN, the ModDown finish written straight into the output (the
+//                     kept limbs) -- the two launches of engine.hip ks_finish_fused.
 //
 // Ranges: the row NTT (table twiddles) leaves |x| <= 17q for q < 2^42 (folded to q/2 + 1 for larger primes
 // before the product); fmul_rem(x, key) lies in (-1.5q, 1.5q) (on-the-fly key quotient), so the
@@ -188,36 +196,17 @@ __device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, con
     wave_lds_sync();  // sr is free again
 }
 
-// grid: 8 * ceil(B / G) * (ne * (R / 8) / 8) blocks of 256 (8 rows x 32 lanes; R = N / 256 rows:
-// 256 or 512); block id -> (xcd group
-// x = id & 7, batch group, pair), pair = (t, 8-row block): all batch groups of one (t, row block)
-// are dealt to one XCD (blocks x, x + 8, ...) so the key rows they share are L2 hits.  G batch
-// elements per workgroup share each key word loaded (G = 2 halves the key reads, the largest
-// load stream of the kernel, at the price of a second pair of accumulators).
-//
-// PROD (relinearisation of a ciphertext product a (x) b, combined ModDown + rescale): no tensor
-// ciphertext exists.  On the Q limbs the prologue reads a0, a1, b0, b1 and forms d0 = a0 b0,
-// d1 = a0 b1 + a1 b0 (the addend, times P) and d2 = a1 b1 (the own digit's limb, times its key
-// words), so the own digit is skipped in the loop; addend = a, d = unused, pb = b.  Products
-// by fmul_rem with the on-the-fly quotient, as the key products: congruent, not canonical,
-// |x| < 3q before the P / key product.  fac (optional; aesfhe_mul_fma): per-prime {alpha, C, K};
-// the product becomes alpha (a (x) b) + C (c0, c1, 0) + (K, 0, 0) (pc = c, absent: no C term),
-// |x| < 4.5q + K before the P / key product.
-//
-// Target limbs t0 .. t0 + nt - 1 only (the grid covers nt limbs).  EPI selects the epilogue:
-// 0 the canonical accumulators into acc; 2 (INV) their inverse row pass instead, raw doubles into
-// acc (ModDown's INTT then runs only its column pass: the dropped limbs of ks_finish_fused);
-// 1 (FIN, G = 1): the
-// ModDown finish of the key switch in the epilogue, for Q limbs t <= lk (engine.hip
-// ks_finish_fused): the limb's two accumulators never reach HBM.  The conv limbs (column pass
-// done, raw doubles, fin.conv[b][c][t]) get their row pass here -- same prime, same row, so the
-// staged twiddles serve them -- and out[b][c][t] = (acc_c - conv_c) D^{-1} (+ fin.add_c) is
-// written canonical; the dropped limbs (t > lk) ran through the non-FIN launch first, into acc.
-// The PROD prologue (see k_nttf_rows_ks below): d0 = a0 b0, d1 = a0 b1 + a1 b0 times P and the own
-// digit's d2 = a1 b1 times its key words, for the lane's 8 elements of (limb t, row).  FMA (the
-// multiply-add of aesfhe_mul_fma, fac != nullptr) is a template argument: with a runtime `if (fac)`
-// inside the element loop every element's 6 operand loads sat behind their own branch and wait
-// (the ISA showed vmcnt(5)..(0) per element), so the prologue's 48 loads were serialised 8 times.
+// PROD (k_nttf_rows_ks_p: relinearisation of a ciphertext product a (x) b, combined ModDown +
+// rescale): no tensor ciphertext exists.  On the Q limbs the prologue reads a0, a1, b0, b1 and
+// forms d0 = a0 b0, d1 = a0 b1 + a1 b0 (the addend, times P) and d2 = a1 b1 (the own digit's limb,
+// times its key words) for the lane's 8 elements of (limb t, row), so the own digit is skipped in
+// the loop; addend = a, d = unused, pb = b.  Products by fmul_rem with the on-the-fly quotient, as
+// the key products: congruent, not canonical, |x| < 3q before the P / key product.  fac (optional;
+// aesfhe_mul_fma): per-prime {alpha, C, K}; the product becomes alpha (a (x) b) + C (c0, c1, 0) +
+// (K, 0, 0) (pc = c, absent: no C term), |x| < 4.5q + K before the P / key product.  FMA
+// (fac != nullptr) is a template argument: with a runtime `if (fac)` inside the element loop every
+// element's 6 operand loads sat behind their own branch and wait (the ISA showed vmcnt(5)..(0) per
+// element), so the prologue's 48 loads were serialised 8 times.
 template <bool FMA>
 __device__ __forceinline__ void ks_prod_prologue(double (&a0)[8], double (&a1)[8], const u64* kp, long kcomp,
                                                  const u64* xa, long aps, const u64* xb, long bps, const u64* xc,
@@ -265,8 +254,19 @@ struct KsFin {
     const double* dinvf;  // D^{-1} mod q_t as w / q
     Opnd2 add;            // plain ModDown (r = 0): the addend joins here, not in the accumulators
 };
+// The unpipelined kernel: every limb t = t0 .. t0 + nt - 1 of one batch element per workgroup,
+// canonical accumulators into acc.  grid: 8 * B * (nt * (R / 8) / 8) blocks of 256 (8 rows x 32
+// lanes; R = N / 256 rows: 256 or 512); block id -> (xcd group x = id & 7, batch element, pair),
+// pair = (t, 8-row block): all batch elements of one (t, row block) are dealt to one XCD (blocks
+// x, x + 8, ...) so the key rows they share are L2 hits.
+// The template parameters and the arguments are those of k_nttf_rows_ks_p (callers and profile
+// readers name the instantiation in full); only G = 1, no PROD, EPI 0 exists, and pb, fac, pc and
+// fin are unused.  The loops over g (batch elements per workgroup, one trip each) and their
+// bb >= B tests stay: writing them out changes hipcc's instruction schedule and scratch use of a
+// kernel whose speed was measured as it stands (tried: 1705 -> 1702..1729 instructions, 20 ->
+// 12..16 B of scratch), and this file's cleanup was to leave every surviving kernel's code alone.
 template <int G, int R = 256, bool PROD = false, int EPI = 0>
-__global__ __launch_bounds__(256, G == 1 ? 4 : 2) void k_nttf_rows_ks(const u64* __restrict__ d, long dbs,
+__global__ __launch_bounds__(256, 4) void k_nttf_rows_ks(const u64* __restrict__ d, long dbs,
                                                       const u64* __restrict__ ext, long exs, long exj,
                                                       const u64* __restrict__ key, long kdig, long kcomp,
                                                       u64* __restrict__ acc, long abs_, long acs, int B,
@@ -274,8 +274,7 @@ __global__ __launch_bounds__(256, G == 1 ? 4 : 2) void k_nttf_rows_ks(const u64*
                                                       const double* __restrict__ pmodf, int accum, Opnd pb,
                                                       const u64* __restrict__ fac, Opnd pc, int t0, int nt,
                                                       KsFin fin) {
-    constexpr bool FIN = EPI == 1, INV = EPI == 2;
-    static_assert(!FIN || G == 1, "the fused finish runs one batch element per workgroup");
+    static_assert(G == 1 && !PROD && EPI == 0, "the accumulating giants' kernel: the other forms are k_nttf_rows_ks_p's");
     // one LDS array (row transposes, then the 8 rows' twiddles -- see row_ntt8_fwd's rt)
     __shared__ double s[8 * 288 + 8 * 256];
     const int nbg = (B + G - 1) / G;
@@ -318,40 +317,7 @@ __global__ __launch_bounds__(256, G == 1 ? 4 : 2) void k_nttf_rows_ks(const u64*
         // operand words at (limb t, row, L + 32 r): base pointers formed once (block-uniform
         // checks), so the 8 loads of each stream issue together (an opnd_get per element put
         // every load behind its own branch and serialised the prologue)
-        if (PROD && t <= l) {
-            const double f = pmodf[t], w = tw_w(f, q);
-            const u64* kp = key + (long)own * kdig + ((long)pid << LOGN) + (long)row * 256 + L;
-            const u64* xa = addend.ptr + (long)(bb & addend.bmask) * addend.bs + roff;
-            const u64* xb = pb.ptr + (long)(bb & pb.bmask) * pb.bs + roff;
-            const u64* xc = pc.ptr ? pc.ptr + (long)(bb & pc.bmask) * pc.bs + roff : xb;
-            const double fal = fac ? (double)fac[3 * t] : 0.0, fC = fac ? (double)fac[3 * t + 1] : 0.0,
-                         fK = fac ? (double)fac[3 * t + 2] : 0.0;
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const double x0 = u2d(xa[32 * r]), x1 = u2d(xa[addend.ps + 32 * r]);
-                const double y0 = u2d(xb[32 * r]), y1 = u2d(xb[pb.ps + 32 * r]);
-                const double kb = u2d(kp[32 * r]), ka = u2d(kp[32 * r + kcomp]);
-                const double y0q = y0 * qi, y1q = y1 * qi;
-                double p0 = fmul_rem(x0, y0, y0q, q);
-                double p1 = fmul_rem(x0, y1, y1q, q) + fmul_rem(x1, y0, y0q, q);
-                double p2 = fmul_rem(x1, y1, y1q, q);
-                if (fac) {  // multiply-add: alpha (a (x) b) + C (c0, c1, 0) + (K, 0, 0)
-                    p0 = fmul_rem(p0, fal, fal * qi, q) + fK;
-                    p1 = fmul_rem(p1, fal, fal * qi, q);
-                    p2 = fmul_rem(p2, fal, fal * qi, q);
-                    if (pc.ptr) {
-                        p0 += fmul_rem(u2d(xc[32 * r]), fC, fC * qi, q);
-                        p1 += fmul_rem(u2d(xc[pc.ps + 32 * r]), fC, fC * qi, q);
-                    }
-                }
-                a0[g][r] = fmul_rem(p0, w, f, q) + fmul_rem(p2, kb, kb * qi, q);
-                a1[g][r] = fmul_rem(p1, w, f, q) + fmul_rem(p2, ka, ka * qi, q);
-                if (big) {
-                    a0[g][r] = fred(a0[g][r], q, qi);
-                    a1[g][r] = fred(a1[g][r], q, qi);
-                }
-            }
-        } else if (!PROD && pmodf && t <= l && addend.ptr) {
+        if (pmodf && t <= l && addend.ptr) {
             const double f = pmodf[t], w = tw_w(f, q);
             const u64* xa = addend.ptr + (long)bb * addend.bs + roff;
             if (addend.np > 0) {
@@ -375,7 +341,6 @@ __global__ __launch_bounds__(256, G == 1 ? 4 : 2) void k_nttf_rows_ks(const u64*
     int nsum = 0;  // digits summed since the last fold (big primes fold every 4)
 #pragma unroll 1
     for (int j = 0; j < beta; j++) {
-        if (PROD && j == own) continue;  // in the prologue (block-uniform)
         // the key digit's words are loaded first: they arrive while the row NTT computes
         const u64* kp = key + (long)j * kdig + ((long)pid << LOGN) + (long)row * 256 + L;
         u64 kbw[8], kaw[8];
@@ -414,61 +379,6 @@ __global__ __launch_bounds__(256, G == 1 ? 4 : 2) void k_nttf_rows_ks(const u64*
                 }
         }
     }
-    if constexpr (FIN) {
-        // ranges: |acc| < 19q and |conv| <= 17q below 2^42 (file header), so |acc - conv| < 2^48;
-        // big primes fold both to q/2 + 1 first -- fmul_rem's input bound either way
-        const int bb = b0;
-        if (bb >= B) return;
-        const double f = fin.dinvf[t], w = tw_w(f, q);
-        const long coff = ((long)t << LOGN) + (long)row * 256;
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            double cv[8];
-            row_ntt8_fwd(cv, fin.conv + (long)bb * fin.cbs + (long)c * fin.cps + coff, sr, L, 1, tw, q, qi, big);
-            const u64* ap = fin.add.ptr && c < fin.add.np ? fin.add.ptr + (long)bb * fin.add.bs + (long)c * fin.add.ps + roff
-                                                          : nullptr;
-            u64* op = fin.out + (long)bb * fin.obs + (long)c * fin.ops + roff;
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                double a = c ? a1[0][r] : a0[0][r];
-                if (big) a = fred(a, q, qi);
-                double v = fmul_rem(a - cv[r], w, f, q);
-                if (ap) v += u2d(ap[32 * r]);
-                __builtin_nontemporal_store(fcanon(v, q, qi), &op[32 * r]);  // streaming
-            }
-        }
-        return;
-    }
-    if constexpr (INV) {
-        // the row's inverse twiddles replace its forward ones in LDS (the row's own 32 lanes;
-        // row_ntt8_stages ended with a wave barrier, so every forward read is done)
-        const double* IW = T.ipsif + ((long)pid << LOGN);
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-            const int e = L + 32 * m;
-            if (e > 0) {
-                const int ml = 1 << (31 - __clz(e));
-                tw[e] = IW[(long)ml * (R + row) + (e - ml)];
-            }
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            const int bb = b0 + g;
-            if (bb >= B) break;
-            u64* o0 = acc + (long)bb * abs_ + roff;
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                double x[8];
-#pragma unroll
-                for (int r = 0; r < 8; r++) x[r] = fred(c ? a1[g][r] : a0[g][r], q, qi);
-                row_intt8(x, sr, L, tw, q, qi, big);
-#pragma unroll
-                for (int r = 0; r < 8; r++) st_d(&o0[(long)c * acs + 32 * r], x[r]);
-            }
-        }
-        return;
-    }
 #pragma unroll
     for (int g = 0; g < G; g++) {
         const int bb = b0 + g;
@@ -492,6 +402,14 @@ __global__ __launch_bounds__(256, G == 1 ? 4 : 2) void k_nttf_rows_ks(const u64*
 // more registers for the staging.  A row pair of a wave is 4 KB contiguous in HBM and lands
 // linearly in the wave's 4 KB of the buffer (4 x 1 KB wave-instructions); the wave that issues a
 // DMA is the one that reads it (after its own vmcnt), so no workgroup barrier is needed.
+//
+// Target limbs t0 .. t0 + nt - 1 only (the grid covers nt limbs).  EPI selects the epilogue:
+// 2 (INV) the accumulators' inverse row pass, raw doubles into acc (ModDown's INTT then runs only
+// its column pass: the dropped limbs t > lk of ks_finish_fused, launched first);
+// 1 (FIN) the ModDown finish of the key switch, for the kept Q limbs t <= lk: the limb's two
+// accumulators never reach HBM.  The conv limbs (column pass done, raw doubles,
+// fin.conv[b][c][t]) get their row pass here -- same prime, same row, so the staged twiddles
+// serve them -- and out[b][c][t] = (acc_c - conv_c) D^{-1} (+ fin.add_c) is written canonical.
 typedef __attribute__((address_space(3))) void ks_lds_void;
 __device__ __forceinline__ void ks_dma_rows(const u64* g, double* lds_wave, int lane) {
 #pragma unroll
@@ -518,7 +436,8 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
                                                       const double* __restrict__ pmodf, int accum, Opnd pb,
                                                       const u64* __restrict__ fac, Opnd pc, int t0, int nt,
                                                       KsFin fin) {
-    constexpr bool FIN = EPI == 1, INV = EPI == 2;
+    static_assert(EPI == 1 || EPI == 2, "FIN or INV: the canonical accumulators are k_nttf_rows_ks's");
+    constexpr bool FIN = EPI == 1;
     // sr (row transposes) | tw (the 8 rows' twiddles) | eb (DMA staging, 2 rows per wave)
     __shared__ double s[8 * 288 + 8 * 256 + 8 * 256];
     const int id = blockIdx.x, x8 = id & 7, rest = id >> 3;
@@ -648,6 +567,8 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
         }
     }
     if constexpr (FIN) {
+        // ranges: |acc| < 19q and |conv| <= 17q below 2^42 (file header), so |acc - conv| < 2^48;
+        // big primes fold both to q/2 + 1 first -- fmul_rem's input bound either way
         const double f = fin.dinvf[t], wv = tw_w(f, q);
         if (beta == 0 || next_digit(-1) >= beta)  // no ext digit: conv row 0 not requested yet
             ks_dma_rows(fin.conv + (long)bb * fin.cbs + coff, ebw, lane);
@@ -674,34 +595,27 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
         }
         return;
     }
-    if constexpr (INV) {
-        const double* IW = T.ipsif + ((long)pid << LOGN);
+    // INV: the row's inverse twiddles replace its forward ones in LDS (the row's own 32 lanes;
+    // row_ntt8_stages ended with a wave barrier, so every forward read is done)
+    const double* IW = T.ipsif + ((long)pid << LOGN);
 #pragma unroll
-        for (int m = 0; m < 8; m++) {
-            const int e = L + 32 * m;
-            if (e > 0) {
-                const int ml = 1 << (31 - __clz(e));
-                tw[e] = IW[(long)ml * (R + row) + (e - ml)];
-            }
+    for (int m = 0; m < 8; m++) {
+        const int e = L + 32 * m;
+        if (e > 0) {
+            const int ml = 1 << (31 - __clz(e));
+            tw[e] = IW[(long)ml * (R + row) + (e - ml)];
         }
-        wave_lds_sync();
-        u64* o0 = acc + (long)bb * abs_ + roff;
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            double x[8];
-#pragma unroll
-            for (int r = 0; r < 8; r++) x[r] = fred(c ? a1[r] : a0[r], q, qi);
-            row_intt8(x, sr, L, tw, q, qi, big);
-#pragma unroll
-            for (int r = 0; r < 8; r++) st_d(&o0[(long)c * acs + 32 * r], x[r]);
-        }
-        return;
     }
+    wave_lds_sync();
     u64* o0 = acc + (long)bb * abs_ + roff;
 #pragma unroll
-    for (int r = 0; r < 8; r++) {
-        __builtin_nontemporal_store(fcanon(a0[r], q, qi), &o0[32 * r]);
-        __builtin_nontemporal_store(fcanon(a1[r], q, qi), &o0[acs + 32 * r]);
+    for (int c = 0; c < 2; c++) {
+        double x[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) x[r] = fred(c ? a1[r] : a0[r], q, qi);
+        row_intt8(x, sr, L, tw, q, qi, big);
+#pragma unroll
+        for (int r = 0; r < 8; r++) st_d(&o0[(long)c * acs + 32 * r], x[r]);
     }
 }
 

@@ -99,7 +99,7 @@ __device__ __forceinline__ void wave_sync_lds() {
 // output is unchanged while the spread's l-limb write + read-back is gone (x[p] is read once per
 // target limb, the same 16-column strip by the same XCD each time: bx's XCD is fixed).  SPREAD 2:
 // x is first multiplied by the level-down constant sc mod q_l (scf = sc / q_l).  SPREAD 3: x mod
-// q_i without centring -- the ModUp of a one-limb key-switch digit (k_modup<1>: hat = hatinv = 1).
+// q_i without centring -- the ModUp of a one-limb key-switch digit (hat = hatinv = 1: no conversion launch).
 // x of poly p at x + p * xs.
 struct SpreadSrc {
     const u64* x;

@@ -261,21 +261,29 @@ def test_dot_fma_bit_exact(product_lib, oracle_lib, gpu_available, kw):
         np.testing.assert_allclose(g.decrypt(cg, sk).real, w, atol=1e-4)
 
 
-@pytest.mark.parametrize("kw", [SMALL, dict(log_n=16, max_level=3, special_primes=2, seed=5),
-                                dict(log_n=16, max_level=12, special_primes=10, seed=5),
-                                dict(log_n=16, max_level=30, special_primes=10, digit_primes=12,
-                                     scale_bits=40, seed=5)],
-                         ids=["n4096", "n65536", "n65536K10", "n65536K10A12"])
-def test_linear_bsgs_bit_exact(product_lib, oracle_lib, gpu_available, kw):
-    """aesfhe_linear_bsgs (hoisted babies and lazy ModDown; at N = 2^16 the giants go through the
-    fused ext-NTT row pass with accumulation) against the oracle's restatement, and its slots
-    against the plain BSGS sum it computes."""
+# (giant, [(baby, diag)]): one key-less and two keyed giants; with a third keyed giant the middle one
+# runs the accumulating launch (accum != 0) and the last one the accumulating finish
+BSGS_PLAN3 = [(0, [(0, 0), (1, 1), (2, 2)]), (-6, [(0, 3)]), (24, [(1, 4), (2, 0)])]
+BSGS_PLAN4 = BSGS_PLAN3 + [(40, [(0, 1), (2, 3)])]
+
+
+@pytest.mark.parametrize("kw,plan", [(SMALL, BSGS_PLAN3),
+                                     (dict(log_n=16, max_level=3, special_primes=2, seed=5), BSGS_PLAN3),
+                                     (dict(log_n=16, max_level=12, special_primes=10, seed=5), BSGS_PLAN3),
+                                     (dict(log_n=16, max_level=30, special_primes=10, digit_primes=12,
+                                           scale_bits=40, seed=5), BSGS_PLAN3),
+                                     (dict(log_n=17, max_level=3, special_primes=2, seed=5), BSGS_PLAN4)],
+                         ids=["n4096", "n65536", "n65536K10", "n65536K10A12", "n131072"])
+def test_linear_bsgs_bit_exact(product_lib, oracle_lib, gpu_available, kw, plan):
+    """aesfhe_linear_bsgs (hoisted babies and lazy ModDown; at N = 2^16 / 2^17 the giants go
+    through the fused ext-NTT row pass with accumulation) against the oracle's restatement, and
+    its slots against the plain BSGS sum it computes.  n131072: three keyed giants at R = 512 --
+    the unpipelined accumulating kernel with earlier sums to add, then the accumulating finish."""
     g, o = _pair(product_lib, oracle_lib, **kw)
     n = g.slot_count
     rng = np.random.default_rng(6)
     z = rng.uniform(-1, 1, (2, n))
     diags = [rng.uniform(-1, 1, n) for _ in range(5)]
-    plan = [(0, [(0, 0), (1, 1), (2, 2)]), (-6, [(0, 3)]), (24, [(1, 4), (2, 0)])]  # (giant, [(baby, diag)])
     babies = [0, 1, -3]
     outs = []
     for eng in (g, o):

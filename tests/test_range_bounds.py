@@ -3,7 +3,7 @@
 The kernels in csrc/ lean on range bounds stated in comments (mul_m: a, b < q < 2^51; fred:
 |x| < 2^53; k_dot: lazy sums folded every 16 pairs; k_rescale_spread: the centring test
 v > (q_l >> 1)) and switch variant by prime size: kBigPrime = 2^42 picks the fold schedule of every
-ntt256f.h pass, of the column base conversions and of k_modup / k_moddown, and poly2_int picks one
+ntt256f.h pass, of the column base conversions and of k_moddown, and poly2_int picks one
 of four kernel classes per limb from the weights' row sums against 2^52 / q and 2^51 / q.  The other
 suites run uniformly random residues on chains whose primes all sit on one side of 2^42.  Here,
 residue for residue against the CPU oracle (np.array_equal on export_residues, inputs through

@@ -29,22 +29,14 @@ CLASSES = [
     (r"k_nttf_rows_ks_p<\d+, false, 1>", "ks_rows_fin.ks"),
     (r"k_nttf_rows_ks_p<\d+, true, 2>", "ks_rows_inner.prod"),
     (r"k_nttf_rows_ks_p<\d+, false, 2>", "ks_rows_inner.ks"),
-    (r"k_nttf_rows_ks_p<\d+, true", "ks_rows_acc.prod"),
-    (r"k_nttf_rows_ks_p<", "ks_rows_acc.ks"),
     (r"k_bconv_cols<\d+, true, false", "modup_cols"),  # round 6: conversion + forward column pass
     (r"k_bconv_cols<\d+, true, true", "moddown_cols"),
     (r"k_bconv_mfma<\d+, false", "modup"),  # matrix-core conversions: ModUp (no v slot), ModDown (v)
     (r"k_bconv_mfma<\d+, true", "moddown"),
     (r"k_bsgs_terms<", "bsgs_terms"),
-    (r"k_nttf_rows_ks<\d+, \d+, true, 1>", "ks_rows_fin.prod"),
-    (r"k_nttf_rows_ks<\d+, \d+, false, 1>", "ks_rows_fin.ks"),
-    (r"k_nttf_rows_ks<\d+, \d+, true, 2>", "ks_rows_inner.prod"),
-    (r"k_nttf_rows_ks<\d+, \d+, false, 2>", "ks_rows_inner.ks"),
-    (r"k_nttf_rows_ks<\d+, \d+, true", "ks_rows_acc.prod"),
-    (r"k_nttf_rows_ks<", "ks_rows_acc.ks"),
+    (r"k_nttf_rows_ks<", "ks_rows_acc.ks"),  # the unpipelined kernel: accumulating giants only
     (r"k_ks_inner_all<", "ks_inner"),
     (r"k_ks_inner_multi<", "ks_inner_multi"),
-    (r"k_modup<", "modup"),
     (r"k_moddown<", "moddown"),
     (r"k_moddown_finish", "moddown_finish"),
     (r"k_poly2_int(_s|_split)?<", "poly2_int"),
