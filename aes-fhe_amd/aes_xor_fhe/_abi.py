@@ -153,6 +153,18 @@ SIGNATURES = [
 
 SYMBOLS = [s[0] for s in SIGNATURES]
 
+# include/aesfhe_ext.h: product-only entry points (batched device plaintexts).  Bound when the
+# library exports all of them (Lib.has_ext); the CPU oracle does not, and the facade then runs the
+# same operation through the calls above, element by element (Engine.multiply_plain_batch).
+c_ptb_p = C.c_void_p
+EXT_SIGNATURES = [
+    ("aesfhe_ptb_create_device", C.c_int, [c_eng_p, C.c_void_p, C.c_int32, C.c_int32, _P(c_ptb_p)]),
+    ("aesfhe_ptb_info", C.c_int, [c_ptb_p, _P(C.c_int32)]),
+    ("aesfhe_ptb_free", None, [c_ptb_p]),
+    ("aesfhe_mul_ptb", C.c_int, [c_eng_p, c_ct_p, c_ptb_p, _P(c_ct_p)]),
+]
+EXT_SYMBOLS = [s[0] for s in EXT_SIGNATURES]
+
 # error code -> exception message prefix (desilofhe raises RuntimeError with text; the
 # reference matches "should have 3 polynomials" at xor_service.py:114-118)
 ERRORS = {-1: "invalid argument", -2: "out of memory", -3: "device error",
@@ -187,6 +199,13 @@ class Lib:
             fn.restype = res
             fn.argtypes = args
             setattr(self, name[len("aesfhe_"):], fn)
+        self.has_ext = all(hasattr(self.cdll, name) for name in EXT_SYMBOLS)
+        if self.has_ext:
+            for name, res, args in EXT_SIGNATURES:
+                fn = getattr(self.cdll, name)
+                fn.restype = res
+                fn.argtypes = args
+                setattr(self, name[len("aesfhe_"):], fn)
         self.backend = self.backend_name().decode()
 
     def check(self, rc: int) -> None:
@@ -224,5 +243,11 @@ def load_product() -> Lib:
         # stray setting cannot turn a GPU test or the bench into the checker comparing itself
         if lib.backend != PRODUCT_BACKEND:
             raise RuntimeError(f"{path} is backend {lib.backend!r}, not the product ({PRODUCT_BACKEND!r})")
+        # the product always carries include/aesfhe_ext.h: a build from before it must not send
+        # Engine.multiply_plain_batch down the checker's per-element path
+        if not lib.has_ext:
+            missing = [s for s in EXT_SYMBOLS if not hasattr(lib.cdll, s)]
+            raise RuntimeError(f"{path}: extension symbols {missing} (include/aesfhe_ext.h) are missing: "
+                               f"rebuild it")
         _PRODUCT = lib
     return _PRODUCT

@@ -28,6 +28,10 @@ final round without MixColumns (depth 4 + 1), with bit-mode bootstrapping
 next round would leave fewer levels than SlotToCoeff needs.  At L = 30: ARK0 -> 29, rounds 1-3
 -> 8, {refresh -> 19, two rounds -> 5} x 2, refresh -> 19, rounds 8-9 and the final round -> 0:
 three refreshes (the bootstrap's output level L - 11).
+
+Counter mode (`AESSlicedRound.keystream_aes128` / `transcipher`): the
+public counter blocks enter as per-element plaintexts times K0 (no encrypted input state), the
+symmetric ciphertext is folded into the last round key: same schedule, same three refreshes.
 """
 from __future__ import annotations
 
@@ -394,15 +398,22 @@ class AESRowRound:
         input state (the largest one, at the top level) is freed if the caller holds it only
         through that list.  probe: optional callable(rnd, state, in_scale) shown every refresh's
         input (refresh_step)."""
-        import time
         bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
-        stc = len(bss[0].stc_bits)
-        assert all(len(b.stc_bits) == stc for b in bss)
         S = self.add_round_key(bits, keys[0])
         if consume:
             self.e.materialize(S)
             for row in bits:
                 row.clear()
+        return self.rounds_1_to_10(S, keys, bss, timings, pairs_per_call, progress, probe)
+
+    def rounds_1_to_10(self, S, keys, bss, timings: dict | None = None, pairs_per_call: int = 8,
+                       progress=None, probe=None):
+        """Rounds 1..10 with their refreshes on the state S = AddRoundKey(k_0) output, under
+        keys[1..10]: what encrypt_aes128 and AESSlicedRound.keystream_aes128 share (arguments as
+        there, bss a list).  Returns the state and the number of refreshes."""
+        import time
+        stc = len(bss[0].stc_bits)
+        assert all(len(b.stc_bits) == stc for b in bss)
         refreshes = 0
         since = 0
         for rnd in range(1, 11):
@@ -508,19 +519,21 @@ class AESSlicedRound(AESRowRound):
         nb = 4 * S if nb is None else int(nb)
         return out.reshape(-1, 16)[:nb * self.n_blk].reshape(nb, self.n_blk, 16)
 
-    def encrypt_blocks_device(self, blocks):
+    def pack_device(self, blocks) -> list:
+        """pack for a (NB, n_blk, 16) uint8 torch tensor, on its device: 4 int64 row tensors."""
         import torch
-        b = blocks.to(self.e.client_device)
+        b = blocks
         nb, S = b.shape[0], self.slabs(b.shape[0])
         flat = torch.zeros((S * self.sc, 16), dtype=torch.uint8, device=b.device)
         flat[:nb * self.n_blk] = b.reshape(-1, 16)
         sl = flat.reshape(S, self.sc, 16)
-        st = []
-        for r in range(4):
-            row = sl[:, :, [r + 4 * c for c in range(4)]].permute(0, 2, 1).reshape(4 * S, self.sc).to(torch.int64)
-            st.append([self.e.encrypt_device(1.0 - 2.0 * ((row >> j) & 1).to(torch.float64), self.pk)
-                       for j in range(8)])
-        return st
+        return [sl[:, :, [r + 4 * c for c in range(4)]].permute(0, 2, 1).reshape(4 * S, self.sc).to(torch.int64)
+                for r in range(4)]
+
+    def encrypt_blocks_device(self, blocks):
+        import torch
+        return [[self.e.encrypt_device(1.0 - 2.0 * ((row >> j) & 1).to(torch.float64), self.pk) for j in range(8)]
+                for row in self.pack_device(blocks.to(self.e.client_device))]
 
     def decrypt_blocks_device(self, bits, nb: int | None = None):
         import torch
@@ -597,3 +610,109 @@ class AESSlicedRound(AESRowRound):
             idx = [4 * s + (c + r) % 4 for s in range(S) for c in range(4)]
             out.append([self.e.gather(c, idx) for c in bits[r]])
         return out
+
+    # ---- counter mode (CTR and the key fold) -------------------------------
+    # XOR with a PUBLIC bit is, in the +-1 domain, a slot-wise sign: a plaintext product with one
+    # plaintext per batch element (every element holds other blocks), Engine.multiply_plain_batch.
+    def _sign_planes(self, rows) -> List[list]:
+        """4 byte rows (4 S, slot_count) -> 4 x 8 arrays of +-1: (-1)^bit j of every byte (numpy
+        rows give numpy planes, torch rows torch planes on their device)."""
+        if isinstance(rows[0], np.ndarray):
+            return [[1.0 - 2.0 * ((row.astype(np.int64) >> j) & 1) for j in range(8)] for row in rows]
+        import torch
+        return [[1.0 - 2.0 * ((row >> j) & 1).to(torch.float64) for j in range(8)] for row in rows]
+
+    def counter_rows_device(self, iv, S: int, first: int, device) -> list:
+        """The packed byte rows of the S * slot_count counter blocks from `first` on
+        (aes_tables.ctr_blocks), computed with torch on `device`: 4 int64 tensors (4 S, slot_count)."""
+        import torch
+        iv = np.asarray(bytearray(iv) if isinstance(iv, (bytes, bytearray)) else iv, dtype=np.uint8)
+        if iv.shape != (16,):
+            raise ValueError("the initial counter block has 16 bytes")
+        n = S * self.sc
+        base = (int.from_bytes(bytes(iv[12:]), "big") + int(first)) % (1 << 32)
+        ctr = (base + torch.arange(n, dtype=torch.int64, device=device)) & 0xFFFFFFFF
+        flat = torch.empty((n, 16), dtype=torch.int64, device=device)
+        flat[:, :12] = torch.as_tensor(iv[:12].astype(np.int64), device=device)
+        for k in range(4):
+            flat[:, 12 + k] = (ctr >> (8 * (3 - k))) & 0xFF
+        sl = flat.reshape(S, self.sc, 16)
+        return [sl[:, :, [r + 4 * c for c in range(4)]].permute(0, 2, 1).reshape(4 * S, self.sc) for r in range(4)]
+
+    def counter_planes(self, iv, nb: int, first: int = 0) -> List[list]:
+        """The +-1 bit planes of the counter blocks of `nb` sets in the sliced layout: planes[r][j]
+        is (4 S, slot_count), element 4 s + c, slot k = (-1)^bit j of byte r + 4c of counter block
+        first + s * slot_count + k (aes_tables.ctr_blocks: inc32).  The padding sets of the last
+        slab get the next counters.  numpy on the CPU oracle; torch on the engine's client device
+        on the HIP engine (nothing but `iv` and `first` crosses the bus)."""
+        S = self.slabs(nb)
+        if self.e.on_device:
+            return self._sign_planes(self.counter_rows_device(iv, S, first, self.e.client_device))
+        return self._sign_planes(self.pack(T.ctr_blocks(iv, S * self.sc, first).reshape(4 * S, self.n_blk, 16)))
+
+    def data_planes(self, data) -> List[list]:
+        """The +-1 bit planes of (NB, n_blk, 16) public bytes (numpy, or a torch tensor: the
+        symmetric ciphertext may already live on the device) in the sliced layout, as
+        counter_planes; the padding sets are zero bytes (+1)."""
+        if self.e.on_device:
+            import torch
+            t = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.array(data, dtype=np.uint8))
+            return self._sign_planes(self.pack_device(t.to(self.e.client_device)))
+        if not isinstance(data, np.ndarray):
+            data = data.cpu().numpy()
+        return self._sign_planes(self.pack(data))
+
+    def mul_planes(self, key, planes) -> List[List[Ciphertext]]:
+        """key[r][j] (batch 4, cycled over the slabs) XOR the public bits planes[r][j] (4 S
+        elements): 32 plaintext products, one level, no key switch.  Each batched plaintext is
+        dropped as soon as its product is enqueued (at N = 2^16 one holds 4 S x (level + 1)
+        limbs)."""
+        e = self.e
+        return [[e.multiply_plain_batch(key[r][j], e.encode_batch(planes[r][j])) for j in range(8)]
+                for r in range(4)]
+
+    def counter_state(self, key0, iv, nb: int, first: int = 0) -> List[List[Ciphertext]]:
+        """AddRoundKey(k_0) of the counter blocks without an encrypted state: K0 times the counter
+        planes, one level below the key's."""
+        return self.mul_planes(key0, self.counter_planes(iv, nb, first))
+
+    def fold_data_key(self, key, data) -> List[List[Ciphertext]]:
+        """The last round key with the public bytes `data` XORed in, K10' = K10 * data planes
+        (batch 4 S, one level below the key's): the final AddRoundKey under it yields
+        keystream XOR data without a level of the state."""
+        return self.mul_planes(key, self.data_planes(data))
+
+    def ctr_key_levels(self, L: int, bss) -> List[int]:
+        """key_levels for keystream_aes128 with `data`: the last key one level higher, the level
+        fold_data_key spends."""
+        lv = self.key_levels(L, bss)
+        return lv[:-1] + [lv[-1] + 1]
+
+    def keystream_aes128(self, iv, nb: int, keys, bs, first: int = 0, data=None, timings: dict | None = None,
+                         pairs_per_call: int = 8, progress=None, probe=None):
+        """AES-128 of the counter blocks first, first + 1, ... of `iv` (aes_tables.ctr_blocks) for
+        `nb` sets of n_blk blocks under the encrypted round keys: the CTR keystream as +-1 bit
+        ciphertexts, with no encrypted input state.  State 0 is counter_state(keys[0], ...) --
+        one level below keys[0], where schedule() puts AddRoundKey(k_0) -- then rounds 1..10 as
+        in encrypt_aes128 (rounds_1_to_10).  With `data` ((nb, n_blk, 16) bytes) the result is
+        keystream XOR data (fold_data_key into keys[10], which must then sit one level above the
+        one round 10 consumes: ctr_key_levels).  `first` lets a rank derive the counters of its
+        own slab range.  Returns the state and the number of refreshes."""
+        bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
+        keys = list(keys)
+        if data is not None:
+            if tuple(data.shape) != (nb, self.n_blk, 16):
+                raise ValueError(f"data must be ({nb}, {self.n_blk}, 16) bytes, got {tuple(data.shape)}")
+            want = self.ctr_key_levels(keys[0][0][0].level, bss)[10]
+            if keys[10][0][0].level < want:
+                raise ValueError(f"keys[10] is at level {keys[10][0][0].level}; folding data into it needs "
+                                 f"level {want} (ctr_key_levels)")
+            keys[10] = self.fold_data_key(keys[10], data)
+        S = self.counter_state(keys[0], iv, nb, first)
+        return self.rounds_1_to_10(S, keys, bss, timings, pairs_per_call, progress, probe)
+
+    def transcipher(self, data, iv, keys, bs, first: int = 0, **kw):
+        """AES-128-CTR decryption of `data` ((NB, n_blk, 16) bytes encrypted from counter `first`
+        of `iv`) under the encrypted round keys: the +-1 bit ciphertexts of the message
+        (decrypt_blocks reads them), and the number of refreshes."""
+        return self.keystream_aes128(iv, data.shape[0], keys, bs, first=first, data=data, **kw)

@@ -128,6 +128,30 @@ def encrypt_block(block: np.ndarray, key: bytes | np.ndarray, rounds: int = 10) 
     return s
 
 
+def ctr_blocks(iv: bytes | np.ndarray, n: int, first: int = 0) -> np.ndarray:
+    """(n, 16) counter blocks: block i is `iv` with its last four bytes, read as a big-endian
+    u32, incremented by first + i modulo 2^32 (inc32, the rule of NIST SP 800-38D and of the usual
+    CTR implementations); the first twelve bytes never change."""
+    iv = np.asarray(bytearray(iv) if isinstance(iv, (bytes, bytearray)) else iv, dtype=np.uint8)
+    if iv.shape != (16,):
+        raise ValueError("the initial counter block has 16 bytes")
+    base = (int.from_bytes(bytes(iv[12:]), "big") + int(first)) % (1 << 32)
+    ctr = (np.uint64(base) + np.arange(int(n), dtype=np.uint64)) & np.uint64(0xFFFFFFFF)
+    out = np.empty((int(n), 16), dtype=np.uint8)
+    out[:, :12] = iv[:12]
+    for k in range(4):
+        out[:, 12 + k] = (ctr >> np.uint64(8 * (3 - k))) & np.uint64(0xFF)
+    return out
+
+
+def ctr_xor(data: np.ndarray, key: bytes | np.ndarray, iv: bytes | np.ndarray, first: int = 0) -> np.ndarray:
+    """AES-128-CTR of `data` ((..., 16) bytes, blocks counted in C order from `first`):
+    encryption and decryption alike."""
+    d = np.asarray(data, dtype=np.uint8)
+    ks = encrypt_block(ctr_blocks(iv, d.size // 16, first), key)
+    return d ^ ks.reshape(d.shape)
+
+
 def aes_round(state: np.ndarray, round_key: np.ndarray) -> np.ndarray:
     """One full middle round: SubBytes -> ShiftRows -> MixColumns -> AddRoundKey."""
     return mix_columns(shift_rows(sub_bytes(state))) ^ round_key

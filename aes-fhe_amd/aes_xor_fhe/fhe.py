@@ -350,6 +350,72 @@ class Plaintext:
         return h._h
 
 
+class PlaintextBatch:
+    """B slot vectors, one per batch element of the ciphertext they multiply (``Plaintext`` is one
+    vector broadcast over the batch).  ``values``: a (B, <= slot_count) numpy array, or a torch
+    tensor on the engine's ``client_device`` (data that already lives on the GPU never visits the
+    host); or ``coeffs``: (B, N) int64 ring coefficients taken as they are.  ``level``: the level
+    the residues are materialised at (None: the level of the ciphertext that uses them).
+
+    The HIP engine encodes and transforms all B on the device (aesfhe_encode_device ->
+    aesfhe_ptb_create_device, include/aesfhe_ext.h) into one handle per (level, scale), made on
+    first use; a backend without the extension (the CPU oracle) has no handle and multiplies
+    element by element through ``element`` (Engine.multiply_plain_batch)."""
+
+    def __init__(self, engine: "Engine", values=None, coeffs=None, level: int | None = None):
+        if (values is None) == (coeffs is None):
+            raise ValueError("PlaintextBatch takes slot values or coefficients")
+        src = values if coeffs is None else coeffs
+        width = engine.slot_count if coeffs is None else 2 * engine.slot_count
+        if src.ndim != 2 or src.shape[0] < 1 or (src.shape[1] > width if coeffs is None else src.shape[1] != width):
+            raise ValueError(f"expected a (B, {'<= ' if coeffs is None else ''}{width}) array, got {tuple(src.shape)}")
+        if level is not None and not 0 <= int(level) <= engine.max_level:
+            raise ValueError(f"level {level} outside 0..{engine.max_level}")
+        self.engine = engine
+        self.values, self.coeffs = values, coeffs
+        self.batch = int(src.shape[0])
+        self.level = None if level is None else int(level)
+        self._dev = {}
+
+    def device(self, level: int, scale: float):
+        """The aesfhe_ptb handle at (level, scale): HIP engine only."""
+        key = (level, scale if self.coeffs is None else None)
+        h = self._dev.get(key)
+        if h is None:
+            import torch
+            eng = self.engine
+            dev = eng.client_device
+            if self.coeffs is not None:
+                co = torch.as_tensor(self.coeffs).to(device=dev, dtype=torch.int64).contiguous()
+                eng._torch_sync()
+            else:
+                co = eng._encode_device(self.values, scale)
+            out = C.c_void_p()
+            eng._check(eng._lib.ptb_create_device(eng._h, co.data_ptr(), self.batch, level, C.byref(out)))
+            h = _Owned(eng._lib, out.value, eng._lib.ptb_free)
+            h.engine = eng
+            eng.synchronize()  # co is read on the engine's stream; torch may recycle it on return
+            self._dev[key] = h
+        return h._h
+
+    def element(self, i: int, level: int, scale: float):
+        """Element i as an aesfhe_pt handle at (level, scale) through the host calls
+        (aesfhe_encode + aesfhe_pt_create): the per-element path of a backend without the
+        extension.  Returns the owning object (its ``_h`` is the handle)."""
+        eng = self.engine
+        if self.coeffs is not None:
+            co = np.ascontiguousarray(np.asarray(self.coeffs)[i], dtype=np.int64)
+        else:
+            v = self.values
+            v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+            co = eng._encode_coeffs(v[i].astype(np.complex128), scale)
+        out = C.c_void_p()
+        eng._check(eng._lib.pt_create(eng._h, _as_ptr(co, C.c_int64), level, C.byref(out)))
+        h = _Owned(eng._lib, out.value, eng._lib.pt_free)
+        h.engine = eng
+        return h
+
+
 # ------------------------------------------------------------------------------------------
 class Engine:
     """CKKS engine with desilofhe's constructor signatures (engine_context.py:27-31):
@@ -696,6 +762,8 @@ class Engine:
             a, b = b, a
         if not isinstance(a, Ciphertext):
             raise TypeError("multiply needs at least one Ciphertext")
+        if isinstance(b, PlaintextBatch):
+            return self.multiply_plain_batch(a, b)
         pt = self._as_plain(b)
         if pt.is_const:
             c = pt.const
@@ -705,6 +773,54 @@ class Engine:
             return self._call_ct(self._lib.mul_const, a._h, c.real, c.imag)
         scale = self._lib.engine_mul_scale(self._h, a.level)
         return self._call_ct(self._lib.mul_pt, a._h, pt.device(a.level, scale))
+
+    def encode_batch(self, values, level: int | None = None) -> PlaintextBatch:
+        """One slot vector per batch element: `values` is a (B, <= slot_count) numpy array or a
+        torch tensor on `client_device` (zero padded to slot_count).  level: the level the
+        residues are materialised at, at least that of the ciphertext they will multiply (None:
+        that ciphertext's).  Nothing is computed until the first product."""
+        import torch
+        if not isinstance(values, torch.Tensor):
+            values = np.asarray(values)
+        return PlaintextBatch(self, values=values, level=level)
+
+    def coeff_batch(self, coeffs, level: int | None = None) -> PlaintextBatch:
+        """encode_batch for plaintexts given as (B, N) int64 ring coefficients, taken as they are
+        (no codec, no scale): a numpy array or a torch tensor on `client_device`."""
+        import torch
+        if not isinstance(coeffs, torch.Tensor):
+            coeffs = np.asarray(coeffs, dtype=np.int64)
+        return PlaintextBatch(self, coeffs=coeffs, level=level)
+
+    def multiply_plain_batch(self, ct: Ciphertext, pb: PlaintextBatch) -> Ciphertext:
+        """Element i of the result is ct[i mod Bc] * pb[i], one level down: the
+        batches are equal or ct's divides pb's (the cyclic rule of multiply(ct, ct)).  The HIP
+        engine runs aesfhe_encode_device -> aesfhe_ptb_create_device -> aesfhe_mul_ptb; a backend
+        without include/aesfhe_ext.h (the CPU oracle, the checker of that path) runs the same
+        arithmetic per element: slice, aesfhe_mul_pt with that element's plaintext, concat."""
+        if pb.engine is not self:
+            raise ValueError("multiply_plain_batch: the plaintexts belong to another engine")
+        level = ct.level if pb.level is None else pb.level
+        # aesfhe_mul_ptb's own refusals, stated here too so that no plaintext is encoded for a
+        # product that cannot run and both backends raise the same way
+        if ct.batch > pb.batch or pb.batch % ct.batch:
+            raise RuntimeError(f"[{self._lib.backend}] invalid argument: batch mismatch {ct.batch} vs "
+                               f"{pb.batch} plaintexts")
+        if ct.level < 1:
+            raise RuntimeError(f"[{self._lib.backend}] level error: no level left for a plaintext multiplication")
+        if level < ct.level:
+            raise RuntimeError(f"[{self._lib.backend}] invalid argument: plaintext level {level} below "
+                               f"ciphertext level {ct.level}")
+        scale = self._lib.engine_mul_scale(self._h, ct.level)
+        if self._lib.has_ext:
+            return self._call_ct(self._lib.mul_ptb, ct._h, pb.device(level, scale))
+        if self.on_device:  # the product never takes the checker's path
+            raise RuntimeError(f"{self._lib.path}: the HIP engine lacks include/aesfhe_ext.h: rebuild it")
+        parts = []
+        for i in range(pb.batch):
+            el, pt = self.slice(ct, i % ct.batch, 1), pb.element(i, level, scale)
+            parts.append(self._call_ct(self._lib.mul_pt, el._h, pt._h))
+        return self.concat(parts)
 
     # -- deferred linear combinations (_LinearCiphertext) -------------------------------------
     def _linear_add(self, a, b):
@@ -1034,12 +1150,11 @@ class Engine:
         if self.on_device:
             torch.cuda.current_stream(self.client_device).synchronize()
 
-    def encrypt_device(self, values, key, level: int | None = None) -> Ciphertext:
-        """Encrypt a (B, <= slot_count) torch tensor of slot values (real or complex) that lives
-        on `client_device`: device encode (aesfhe_encode_device, bit-identical to the host codec)
-        and encryption (aesfhe_encrypt_device), no host copy.  Same nonce sequence as encrypt."""
+    def _encode_device(self, values, scale: float):
+        """(B, <= slot_count) slot values (a torch tensor, moved to `client_device` if it is not
+        there, or anything numpy reads) -> the (B, N) int64 coefficient tensor at `scale`
+        (aesfhe_encode_device: bit-identical to the host codec, synchronises)."""
         import torch
-        level = self.max_level if level is None else int(level)
         dev = self.client_device
         t = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.asarray(values))
         t = t.to(dev)
@@ -1055,7 +1170,16 @@ class Engine:
         co = torch.empty((B, 1 << self.log_coeff_count), dtype=torch.int64, device=dev)
         self._torch_sync()  # the slot tensors are written on torch's stream
         self._check(self._lib.encode_device(self._h, re.data_ptr(), im.data_ptr() if im is not None else None,
-                                            B, ns, ns, self.scales[level], co.data_ptr()))
+                                            B, ns, ns, scale, co.data_ptr()))
+        return co
+
+    def encrypt_device(self, values, key, level: int | None = None) -> Ciphertext:
+        """Encrypt a (B, <= slot_count) torch tensor of slot values (real or complex) that lives
+        on `client_device`: device encode (aesfhe_encode_device, bit-identical to the host codec)
+        and encryption (aesfhe_encrypt_device), no host copy.  Same nonce sequence as encrypt."""
+        level = self.max_level if level is None else int(level)
+        co = self._encode_device(values, self.scales[level])
+        B = co.shape[0]
         nonce = self._nonce
         self._nonce += 1
         out = C.c_void_p()

@@ -1,0 +1,51 @@
+/*
+ * aesfhe_ext.h -- product-only extension of the C ABI of include/aesfhe.h: batched plaintexts
+ * created from coefficients that already live in the engine's device memory, and the ciphertext
+ * product against them (one plaintext PER batch element, where aesfhe_mul_pt / aesfhe_dot_pt
+ * broadcast a single host-made plaintext over the batch).
+ *
+ * Why it exists: XOR with public per-block data (AES-CTR: the counter blocks, the symmetric
+ * ciphertext) is, in the +-1 bit domain of aes_round_bits, a slot-wise sign -- a plaintext
+ * product -- and in the sliced layout every batch element holds other blocks.  No reference
+ * counterpart (the reference has no counter mode); the unfused equivalent through aesfhe.h is,
+ * per element, aesfhe_ct_slice + aesfhe_pt_create + aesfhe_mul_pt, then aesfhe_ct_concat, which
+ * is also what the CPU oracle runs as the checker (Engine.multiply_plain_batch's fallback).
+ *
+ * Only libaesfhe.so (HIP, gfx950) exports these; the oracle does not, and AESFHE_ABI_VERSION is
+ * unchanged.  Conventions (error codes, handles, aesfhe_last_error) are those of aesfhe.h.
+ */
+#ifndef AESFHE_EXT_H
+#define AESFHE_EXT_H
+
+#include "aesfhe.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct aesfhe_ptb aesfhe_ptb;
+
+/* batch x N int64 coefficients in the engine's device memory (as aesfhe_encode_device writes
+ * them) -> NTT residues [batch][level + 1][N].  Per element aesfhe_pt_create's arithmetic: the
+ * signed coefficient reduced mod every q_i, then the forward NTT.  Stream-ordered on the engine's
+ * stream: no host copy, no synchronisation (the caller keeps coeffs_dev alive until the stream
+ * has passed this call). */
+int aesfhe_ptb_create_device(aesfhe_engine *eng, const int64_t *coeffs_dev, int32_t batch,
+                             int32_t level, aesfhe_ptb **out);
+/* info[0]=batch info[1]=level */
+int aesfhe_ptb_info(const aesfhe_ptb *ptb, int32_t info[2]);
+void aesfhe_ptb_free(aesfhe_ptb *ptb);
+
+/* Element i of the result (batch Bp = ptb's) is ct[i mod Bc] (*) ptb[i], rescaled to level - 1:
+ * word for word aesfhe_mul_pt of that ciphertext element with that plaintext.  Bc == Bp, or
+ * Bc < Bp with Bp % Bc == 0 (the cyclic rule of aesfhe_mul); anything else is AESFHE_EARG.
+ * ptb->level >= ct->level (the plaintext's extra limbs are skipped by its own limb stride), the
+ * plaintexts encoded at the aesfhe_engine_mul_scale of ct->level.  A level-0 ciphertext is
+ * AESFHE_ELEVEL; a zero ciphertext gives a zero ciphertext. */
+int aesfhe_mul_ptb(aesfhe_engine *eng, const aesfhe_ct *ct, const aesfhe_ptb *ptb,
+                   aesfhe_ct **out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* AESFHE_EXT_H */
