@@ -27,6 +27,7 @@
 #include "bconv_mfma.h"
 #include "bconv_cols.h"
 #include "bsgs_plan.h"
+#include "operands.h"
 #include "arena.h"
 #include "codec_dev.h"
 
@@ -319,6 +320,32 @@ static T* upload_small(aesfhe_engine* e, const T* src, size_t count) {
     return dst;
 }
 
+// The arrays of operand tables (operands.h) on the device.  Array by array over the tables (every
+// table's pointers, then every table's batch strides, ...), the arrays `fields` names only; an
+// empty array is not uploaded (nullptr).
+struct DevOperands {
+    const u64* const* ptr = nullptr;
+    const long *bs = nullptr, *ps = nullptr;
+    const int* np = nullptr;
+};
+enum { OP_PTR = 1, OP_BS = 2, OP_PS = 4, OP_NP = 8 };
+static std::vector<DevOperands> upload(aesfhe_engine* e, std::initializer_list<const OperandTable*> tabs, int fields) {
+    std::vector<DevOperands> d(tabs.size());
+    auto array = [&](int bit, auto OperandTable::*src, auto DevOperands::*dst) {
+        if (!(fields & bit)) return;
+        size_t i = 0;
+        for (const OperandTable* t : tabs) {
+            if (!(t->*src).empty()) d[i].*dst = upload_small(e, (t->*src).data(), (t->*src).size());
+            i++;
+        }
+    };
+    array(OP_PTR, &OperandTable::ptr, &DevOperands::ptr);
+    array(OP_BS, &OperandTable::bs, &DevOperands::bs);
+    array(OP_PS, &OperandTable::ps, &DevOperands::ps);
+    array(OP_NP, &OperandTable::np, &DevOperands::np);
+    return d;
+}
+
 // AESFHE_POOL_POISON=1 (diagnostic): every pool block handed out is first filled with 0xA5 bytes on
 // the engine stream, so a read of words nobody wrote is deterministic (and loud) instead of
 // whatever the block held before
@@ -333,65 +360,77 @@ static void* pool_get(aesfhe_engine* e, size_t bytes, bool tmp = false) {
 static u64* dalloc(aesfhe_engine* e, size_t words) { return (u64*)pool_get(e, words * 8, true); }
 static void dfree(aesfhe_engine* e, u64* p, size_t words) { e->pool.put(p, words * 8); }
 
-struct Tmp {  // RAII temporary device buffer from the pool
-    aesfhe_engine* e;
-    u64* p;
-    size_t w;
+struct Tmp {  // RAII temporary device buffer from the pool; empty by default, movable
+    aesfhe_engine* e = nullptr;
+    u64* p = nullptr;
+    size_t w = 0;
+    Tmp() = default;
     Tmp(aesfhe_engine* e_, size_t words) : e(e_), p(dalloc(e_, words)), w(words) {}
-    ~Tmp() { dfree(e, p, w); }
+    Tmp(Tmp&& o) noexcept : e(o.e), p(o.p), w(o.w) { o.p = nullptr; }
+    Tmp& operator=(Tmp&& o) noexcept {
+        std::swap(e, o.e), std::swap(p, o.p), std::swap(w, o.w);
+        o.reset();
+        return *this;
+    }
+    ~Tmp() { reset(); }
+    void reset() {  // back to the pool now (stream-ordered: reused only by later work)
+        if (p) dfree(e, p, w);
+        p = nullptr;
+    }
+    explicit operator bool() const { return p != nullptr; }
 };
 
-static aesfhe_ct* ct_new(aesfhe_engine* e, int B, int np, int level) {
-    auto* c = new aesfhe_ct;
-    c->eng = e;
+// Owning handle of a ciphertext made inside the engine: its block goes back to the pool (and its
+// engine reference is dropped) when the handle dies, on error paths too.  Ownership leaves the
+// engine only at `*out = x.release()`.
+struct CtFree {
+    void operator()(aesfhe_ct* c) const { aesfhe_ct_free(c); }
+};
+using CtPtr = std::unique_ptr<aesfhe_ct, CtFree>;
+
+// hand every ciphertext of v to the caller (after the last step that can throw)
+static void release_all(std::vector<CtPtr>& v, aesfhe_ct** outs) {
+    for (size_t i = 0; i < v.size(); i++) outs[i] = v[i].release();
+}
+
+static CtPtr ct_new(aesfhe_engine* e, int B, int np, int level) {
+    auto* c = new aesfhe_ct{e, B, np, level, 0, nullptr, 0};  // d == nullptr: freeing it puts nothing back
     e->refs++;
-    c->B = B;
-    c->np = np;
-    c->level = level;
-    c->is_zero = 0;
+    CtPtr h(c);
     c->bytes = (size_t)B * np * (level + 1) * e->N * 8;
     c->d = (u64*)pool_get(e, c->bytes);
-    return c;
+    return h;
 }
 
 // The m outputs of a batched result r (batch m * B, output t = elements t*B .. t*B + B - 1) as m
 // ciphertexts of batch B sharing r's device block (split in the pool, no copy); r is consumed.
-static std::vector<aesfhe_ct*> ct_split_batch(aesfhe_engine* e, aesfhe_ct* r, int m) {
+static std::vector<CtPtr> ct_split_batch(aesfhe_engine* e, CtPtr r, int m) {
     const int B = r->B / m;
     const size_t part = (size_t)B * r->np * (r->level + 1) * e->N * 8;
-    e->pool.split(r->d, m, part);
-    std::vector<aesfhe_ct*> out(m);
-    for (int t = 0; t < m; t++) {
-        auto* c = new aesfhe_ct;
-        c->eng = e;
+    std::vector<CtPtr> out(m);
+    for (int t = 0; t < m; t++) {  // empty parts first: nothing below can fail between the split and the hand-over
+        out[t].reset(new aesfhe_ct{e, B, r->np, r->level, 0, nullptr, 0});
         e->refs++;
-        c->B = B;
-        c->np = r->np;
-        c->level = r->level;
-        c->is_zero = 0;
-        c->bytes = part;
-        c->d = (u64*)((char*)r->d + (size_t)t * part);
-        out[t] = c;
+    }
+    e->pool.split(r->d, m, part);
+    for (int t = 0; t < m; t++) {
+        out[t]->bytes = part;
+        out[t]->d = (u64*)((char*)r->d + (size_t)t * part);
     }
     r->d = nullptr;  // the blocks now belong to the parts
-    aesfhe_ct_free(r);
+    aesfhe_ct_free(r.release());
     return out;
 }
 
-static aesfhe_ct* ct_zero_new(aesfhe_engine* e, int B, int np, int level) {
-    aesfhe_ct* c = ct_new(e, B, np, level);
+static CtPtr ct_zero_new(aesfhe_engine* e, int B, int np, int level) {
+    CtPtr c = ct_new(e, B, np, level);
     HIPC(hipMemsetAsync(c->d, 0, c->bytes, e->stream));
     c->is_zero = 1;
     return c;
 }
 
-// A (possibly strided / truncated / broadcast) view of ciphertext data.
-struct View {
-    const u64* d;
-    int B, np, level;
-    long ps, bs;  // poly stride, batch stride (0 = broadcast)
-    bool zero;
-};
+// A (possibly strided / truncated / broadcast) view of ciphertext data (operands.h).
+using View = Operand;
 
 static View view_of(const aesfhe_ct* c) {
     View v;
@@ -408,7 +447,7 @@ static View view_of(const aesfhe_ct* c) {
 static Opnd opnd(const View& v, int outB) {
     Opnd o;
     o.ptr = v.zero ? nullptr : v.d;
-    o.bs = (v.B == 1 && outB > 1) ? 0 : v.bs;
+    o.bs = bcast_stride(v.B, v.bs, outB);
     o.ps = v.ps;
     o.np = v.np;
     o.bmask = (v.B > 1 && v.B < outB) ? v.B - 1 : -1;  // cyclic broadcast (check_cyclic)
@@ -422,6 +461,9 @@ static Out out_of(aesfhe_ct* c) {
     o.bs = (long)c->np * o.ps;
     return o;
 }
+
+static View view_of(const CtPtr& c) { return view_of(c.get()); }
+static Out out_of(const CtPtr& c) { return out_of(c.get()); }
 
 static dim3 ew_grid(aesfhe_engine* e, int y, int z) { return dim3(e->N / 256, y, z); }
 
@@ -1312,10 +1354,10 @@ extern "C" int aesfhe_ct_import(aesfhe_engine* e, const uint64_t* in, int32_t B,
                                 int32_t level, aesfhe_ct** out) {
     API_BEGIN
     if (B < 1 || np < 1 || np > 3 || level < 0 || level > e->L) throw_err(AESFHE_EARG, "bad shape");
-    aesfhe_ct* c = ct_new(e, B, np, level);
+    CtPtr c = ct_new(e, B, np, level);
     HIPC(hipMemcpyAsync(c->d, in, c->bytes, hipMemcpyHostToDevice, e->stream));
     HIPC(hipStreamSynchronize(e->stream));
-    *out = c;
+    *out = c.release();
     API_END
 }
 // Device-resident transfer (the multi-GPU scatter/gather, parallel.py): residues of batch
@@ -1334,10 +1376,10 @@ extern "C" int aesfhe_ct_import_device(aesfhe_engine* e, const void* src, int32_
                                        aesfhe_ct** out) {
     API_BEGIN
     if (!src || B < 1 || np < 1 || np > 3 || level < 0 || level > e->L) throw_err(AESFHE_EARG, "bad shape");
-    aesfhe_ct* c = ct_new(e, B, np, level);
+    CtPtr c = ct_new(e, B, np, level);
     HIPC(hipMemcpyAsync(c->d, src, c->bytes, hipMemcpyDeviceToDevice, e->stream));
     HIPC(hipStreamSynchronize(e->stream));
-    *out = c;
+    *out = c.release();
     API_END
 }
 
@@ -1405,22 +1447,25 @@ extern "C" int aesfhe_key_trim(aesfhe_engine* e, aesfhe_key* k, int32_t max_leve
     }
     API_END
 }
-extern "C" int aesfhe_ct_copy(aesfhe_engine* e, const aesfhe_ct* c, aesfhe_ct** out) {
-    API_BEGIN
-    aesfhe_ct* r = ct_new(e, c->B, c->np, c->level);
+static CtPtr ct_copy_new(aesfhe_engine* e, const aesfhe_ct* c) {
+    CtPtr r = ct_new(e, c->B, c->np, c->level);
     HIPC(hipMemcpyAsync(r->d, c->d, c->bytes, hipMemcpyDeviceToDevice, e->stream));
     r->is_zero = c->is_zero;
-    *out = r;
+    return r;
+}
+extern "C" int aesfhe_ct_copy(aesfhe_engine* e, const aesfhe_ct* c, aesfhe_ct** out) {
+    API_BEGIN
+    *out = ct_copy_new(e, c).release();
     API_END
 }
 extern "C" int aesfhe_ct_slice(aesfhe_engine* e, const aesfhe_ct* c, int32_t start, int32_t count, aesfhe_ct** out) {
     API_BEGIN
     if (start < 0 || count < 1 || start + count > c->B) throw_err(AESFHE_EARG, "bad slice");
-    aesfhe_ct* r = ct_new(e, count, c->np, c->level);
+    CtPtr r = ct_new(e, count, c->np, c->level);
     size_t per = c->bytes / c->B;
     HIPC(hipMemcpyAsync(r->d, (char*)c->d + per * start, per * count, hipMemcpyDeviceToDevice, e->stream));
     r->is_zero = c->is_zero;
-    *out = r;
+    *out = r.release();
     API_END
 }
 extern "C" int aesfhe_ct_concat(aesfhe_engine* e, const aesfhe_ct* const* parts, int32_t n, aesfhe_ct** out) {
@@ -1433,14 +1478,14 @@ extern "C" int aesfhe_ct_concat(aesfhe_engine* e, const aesfhe_ct* const* parts,
         B += parts[i]->B;
         allz &= parts[i]->is_zero;
     }
-    aesfhe_ct* r = ct_new(e, B, parts[0]->np, parts[0]->level);
+    CtPtr r = ct_new(e, B, parts[0]->np, parts[0]->level);
     size_t off = 0;
     for (int i = 0; i < n; i++) {
         HIPC(hipMemcpyAsync((char*)r->d + off, parts[i]->d, parts[i]->bytes, hipMemcpyDeviceToDevice, e->stream));
         off += parts[i]->bytes;
     }
     r->is_zero = allz;
-    *out = r;
+    *out = r.release();
     API_END
 }
 extern "C" int aesfhe_ct_gather(aesfhe_engine* e, const aesfhe_ct* c, const int32_t* idx, int32_t n, aesfhe_ct** out) {
@@ -1448,7 +1493,7 @@ extern "C" int aesfhe_ct_gather(aesfhe_engine* e, const aesfhe_ct* c, const int3
     if (n < 1 || !idx) throw_err(AESFHE_EARG, "empty gather");
     for (int b = 0; b < n; b++)
         if (idx[b] < 0 || idx[b] >= c->B) throw_err(AESFHE_EARG, "gather index out of range");
-    aesfhe_ct* r = ct_new(e, n, c->np, c->level);
+    CtPtr r = ct_new(e, n, c->np, c->level);
     const long per = (long)(c->bytes / c->B / 8);  // np * (level + 1) * N words
     const int* di = upload_small(e, (const int*)idx, (size_t)n);
     const long blocks = std::min<long>(per / 512, 256);
@@ -1458,13 +1503,13 @@ extern "C" int aesfhe_ct_gather(aesfhe_engine* e, const aesfhe_ct* c, const int3
                            (const u64*)c->d, r->d, di, per);
     }
     r->is_zero = c->is_zero;
-    *out = r;
+    *out = r.release();
     API_END
 }
 extern "C" int aesfhe_ct_zero(aesfhe_engine* e, int32_t B, int32_t level, aesfhe_ct** out) {
     API_BEGIN
     if (B < 1 || level < 0 || level > e->L) throw_err(AESFHE_EARG, "bad zero shape");
-    *out = ct_zero_new(e, B, 2, level);
+    *out = ct_zero_new(e, B, 2, level).release();
     API_END
 }
 
@@ -1521,20 +1566,20 @@ extern "C" void aesfhe_pt_free(aesfhe_pt* p) {
 // encryption / decryption
 // encryption of B coefficient vectors (int64, B x N) held on the host (aesfhe_encrypt) or on the
 // device (aesfhe_encrypt_device)
-static aesfhe_ct* encrypt_coeffs(aesfhe_engine* e, const aesfhe_key* key, const int64_t* co, int B, int level,
-                                 uint64_t nonce, bool host) {
+static CtPtr encrypt_coeffs(aesfhe_engine* e, const aesfhe_key* key, const int64_t* co, int B, int level,
+                            uint64_t nonce, bool host) {
     if (!key || (key->kind != 0 && key->kind != 1)) throw_err(AESFHE_EARG, "encryption key must be pk or sk");
     if (level < 0 || level > e->L || B < 1) throw_err(AESFHE_EARG, "bad level/batch");
     const int N = e->N, nl = level + 1;
     const long step = (long)nl * N;
-    aesfhe_ct* c = ct_new(e, B, 2, level);
+    CtPtr c = ct_new(e, B, 2, level);
     Tmp vem(e, (size_t)B * 4 * step);
-    std::unique_ptr<Tmp> hco;
+    Tmp hco;
     const u64* dcop = (const u64*)co;
     if (host) {
-        hco.reset(new Tmp(e, (size_t)B * N));
-        HIPC(hipMemcpyAsync(hco->p, co, (size_t)B * N * 8, hipMemcpyHostToDevice, e->stream));
-        dcop = hco->p;
+        hco = Tmp(e, (size_t)B * N);
+        HIPC(hipMemcpyAsync(hco.p, co, (size_t)B * N * 8, hipMemcpyHostToDevice, e->stream));
+        dcop = hco.p;
     }
     const u64 base = derive(derive(e->seed, 0xE0CULL), nonce);
     std::vector<u64> k0s(B);
@@ -1569,7 +1614,7 @@ static aesfhe_ct* encrypt_coeffs(aesfhe_engine* e, const aesfhe_key* key, const 
 extern "C" int aesfhe_encrypt(aesfhe_engine* e, const aesfhe_key* key, const int64_t* co, int32_t B,
                               int32_t level, uint64_t nonce, aesfhe_ct** out) {
     API_BEGIN
-    *out = encrypt_coeffs(e, key, co, B, level, nonce, true);
+    *out = encrypt_coeffs(e, key, co, B, level, nonce, true).release();
     API_END
 }
 
@@ -1676,7 +1721,7 @@ extern "C" int aesfhe_encrypt_device(aesfhe_engine* e, const aesfhe_key* key, co
                                      int32_t level, uint64_t nonce, aesfhe_ct** out) {
     API_BEGIN
     if (!co) throw_err(AESFHE_EARG, "null coefficient buffer");
-    *out = encrypt_coeffs(e, key, co, B, level, nonce, false);
+    *out = encrypt_coeffs(e, key, co, B, level, nonce, false).release();
     API_END
 }
 
@@ -1717,9 +1762,11 @@ extern "C" int aesfhe_decrypt_device(aesfhe_engine* e, const aesfhe_key* sk, con
 static void const_factors(aesfhe_engine* e, int64_t A, int64_t Bc, int nl, std::vector<u64>& f, std::vector<double>& ff);
 // into: write the result into this caller-owned compact block (in.B x in.np polys at level l-1)
 // instead of a new ciphertext (the return value is then nullptr).
-static aesfhe_ct* rescale_view(aesfhe_engine* e, const View& in, int64_t C = 1, u64* into = nullptr) {
+static CtPtr rescale_view(aesfhe_engine* e, const View& in, int64_t C = 1, u64* into = nullptr) {
     const int N = e->N, l = in.level, P = in.B * in.np;
     const bool sc = C != 1;
+    // the flattened-poly Span below requires bs == np*ps, true for compact views
+    if (!in.compact() && in.B > 1) throw_err(AESFHE_EARG, "rescale of non-compact view");
     u64* df = nullptr;
     double* dff = nullptr;
     double* dff_c = nullptr;
@@ -1737,15 +1784,15 @@ static aesfhe_ct* rescale_view(aesfhe_engine* e, const View& in, int64_t C = 1, 
         for (int i = 0; i < l; i++) fc[i] = ff[2 * i];
         dff_c = upload_small(e, fc.data(), fc.size());
     }
-    aesfhe_ct* r = into ? nullptr : ct_new(e, in.B, in.np, l - 1);
+    CtPtr r;
+    if (!into) r = ct_new(e, in.B, in.np, l - 1);
     aesfhe_ct alias{e, in.B, in.np, l - 1, 0, into, 0};
-    aesfhe_ct* o = into ? &alias : r;
+    aesfhe_ct* o = into ? &alias : r.get();
     Tmp x(e, (size_t)P * N), t(e, (size_t)P * l * N);
     // INTT of limb l of every poly: source poly p of batch b at d + b*bs + p*ps + l*N
-    // (expressed as a Span over the flattened polys; requires bs == np*ps, true for compact views)
+    // (expressed as a Span over the flattened polys)
     Span src = span_s((u64*)in.d + (long)l * N, in.ps, 1, 1, l, e->Lp1);
     Span dx = span_s(x.p, N, 1, 1, l, e->Lp1);
-    if (in.bs != (long)in.np * in.ps && in.B > 1) throw_err(AESFHE_EARG, "rescale of non-compact view");
     ntt(e, src, dx, P, true);
     Span st = span_s(t.p, (long)l * N, l, l, 0, e->Lp1);
     if (fused_ntt(e) && in.np == 2 && !in.zero) {
@@ -1781,16 +1828,19 @@ static aesfhe_ct* rescale_view(aesfhe_engine* e, const View& in, int64_t C = 1, 
 
 // rescale of a compact buffer holding G groups of Bg batch elements (np polys, level l) into G
 // new ciphertexts at level l-1 (one rescale pass for all groups)
-static std::vector<aesfhe_ct*> rescale_groups(aesfhe_engine* e, const u64* d, int G, int Bg, int np, int l) {
+static std::vector<CtPtr> rescale_groups(aesfhe_engine* e, const u64* d, int G, int Bg, int np, int l) {
     const int N = e->N, P = G * Bg * np;
     if (fused_ntt(e) && np == 2) {
         // the groups are one compact batch of G * Bg ciphertexts: the fused rescale (spread in the
         // column pass, finish in the row pass), then the output block split per group (no copies)
         const long ps = (long)(l + 1) * N;
-        aesfhe_ct* r = rescale_view(e, View{d, G * Bg, np, l, ps, np * ps, false});
-        return G == 1 ? std::vector<aesfhe_ct*>{r} : ct_split_batch(e, r, G);
+        CtPtr r = rescale_view(e, View{d, G * Bg, np, l, ps, np * ps, false});
+        if (G > 1) return ct_split_batch(e, std::move(r), G);
+        std::vector<CtPtr> one;
+        one.push_back(std::move(r));
+        return one;
     }
-    std::vector<aesfhe_ct*> outs(G);
+    std::vector<CtPtr> outs(G);
     for (int g = 0; g < G; g++) outs[g] = ct_new(e, Bg, np, l - 1);
     Tmp x(e, (size_t)P * N), t(e, (size_t)P * l * N);
     const long cps = (long)(l + 1) * N;
@@ -1847,17 +1897,12 @@ static int64_t level_down_const(const aesfhe_engine* e, int from, int lt) {
     return llround(e->chain.scale[lt] * (double)e->chain.q[lt + 1] / e->chain.scale[from]);
 }
 
-static aesfhe_ct* level_down_view(aesfhe_engine* e, const View& v, int lt) {
+static CtPtr level_down_view(aesfhe_engine* e, const View& v, int lt) {
     if (lt == v.level) {
-        aesfhe_ct* r = ct_new(e, v.B, v.np, v.level);
-        if (v.zero) {
-            HIPC(hipMemsetAsync(r->d, 0, r->bytes, e->stream));
-            r->is_zero = 1;
-        } else if (v.bs == (long)v.np * v.ps) {
-            HIPC(hipMemcpyAsync(r->d, v.d, r->bytes, hipMemcpyDeviceToDevice, e->stream));
-        } else {
-            throw_err(AESFHE_EARG, "copy of non-compact view");
-        }
+        if (v.zero) return ct_zero_new(e, v.B, v.np, v.level);
+        if (!v.compact()) throw_err(AESFHE_EARG, "copy of non-compact view");
+        CtPtr r = ct_new(e, v.B, v.np, v.level);
+        HIPC(hipMemcpyAsync(r->d, v.d, r->bytes, hipMemcpyDeviceToDevice, e->stream));
         return r;
     }
     if (v.zero) return ct_zero_new(e, v.B, v.np, lt);
@@ -1867,11 +1912,8 @@ static aesfhe_ct* level_down_view(aesfhe_engine* e, const View& v, int lt) {
 
 // owned-or-borrowed aligned operand
 struct Aligned {
-    aesfhe_ct* owned = nullptr;
+    CtPtr owned;
     View v;
-    ~Aligned() {
-        if (owned) aesfhe_ct_free(owned);
-    }
 };
 
 static void align_to(aesfhe_engine* e, const aesfhe_ct* c, int l, Aligned& a) {
@@ -1891,6 +1933,12 @@ static View trunc_view(const aesfhe_ct* c, int l) {
     return v;
 }
 
+static std::vector<Operand> views_of(const aesfhe_ct* const* c, int n) {
+    std::vector<Operand> v(n);
+    for (int i = 0; i < n; i++) v[i] = view_of(c[i]);
+    return v;
+}
+
 static void check_bcast(int a, int b) {
     if (a != b && a != 1 && b != 1) throw_err(AESFHE_EARG, "batch mismatch %d vs %d", a, b);
 }
@@ -1905,15 +1953,15 @@ static void check_cyclic(int a, int b) {
 extern "C" int aesfhe_rescale(aesfhe_engine* e, const aesfhe_ct* c, aesfhe_ct** out) {
     API_BEGIN
     if (c->level < 1) throw_err(AESFHE_ELEVEL, "cannot rescale a level-0 ciphertext");
-    if (c->is_zero) *out = ct_zero_new(e, c->B, c->np, c->level - 1);
-    else *out = rescale_view(e, view_of(c));
+    if (c->is_zero) *out = ct_zero_new(e, c->B, c->np, c->level - 1).release();
+    else *out = rescale_view(e, view_of(c)).release();
     API_END
 }
 
 extern "C" int aesfhe_level_down(aesfhe_engine* e, const aesfhe_ct* c, int32_t lt, aesfhe_ct** out) {
     API_BEGIN
     if (lt < 0 || lt > c->level) throw_err(AESFHE_EARG, "level_down target %d not in [0,%d]", lt, c->level);
-    *out = level_down_view(e, view_of(c), lt);
+    *out = level_down_view(e, view_of(c), lt).release();
     API_END
 }
 
@@ -1925,35 +1973,35 @@ static int addsub(aesfhe_engine* e, const aesfhe_ct* a, const aesfhe_ct* b, int 
     align_to(e, a, l, A);
     align_to(e, b, l, Bv);
     int B = std::max(a->B, b->B), np = std::max(a->np, b->np);
-    aesfhe_ct* r = ct_new(e, B, np, l);
+    CtPtr r = ct_new(e, B, np, l);
     ProfScope ps(e, FAM_EW, 24.0 * e->N * (l + 1) * (double)B * np, "add");
     hipLaunchKernelGGL(k_addsub, ew_grid(e, l + 1, B * np), dim3(256), 0, e->stream, opnd(A.v, B), opnd(Bv.v, B), out_of(r), np, e->q, sub, e->logN);
     HIPC(hipGetLastError());
     r->is_zero = a->is_zero && b->is_zero;
-    *out = r;
+    *out = r.release();
     API_END
 }
 extern "C" int aesfhe_add(aesfhe_engine* e, const aesfhe_ct* a, const aesfhe_ct* b, aesfhe_ct** out) { return addsub(e, a, b, 0, out); }
 extern "C" int aesfhe_sub(aesfhe_engine* e, const aesfhe_ct* a, const aesfhe_ct* b, aesfhe_ct** out) { return addsub(e, a, b, 1, out); }
 extern "C" int aesfhe_negate(aesfhe_engine* e, const aesfhe_ct* a, aesfhe_ct** out) {
     API_BEGIN
-    aesfhe_ct* r = ct_new(e, a->B, a->np, a->level);
+    CtPtr r = ct_new(e, a->B, a->np, a->level);
     View z = view_of(a);
     z.zero = true;
     hipLaunchKernelGGL(k_addsub, ew_grid(e, a->level + 1, a->B * a->np), dim3(256), 0, e->stream, opnd(z, a->B), opnd(view_of(a), a->B), out_of(r), a->np, e->q, 1, e->logN);
     HIPC(hipGetLastError());
     r->is_zero = a->is_zero;
-    *out = r;
+    *out = r.release();
     API_END
 }
 
 extern "C" int aesfhe_add_pt(aesfhe_engine* e, const aesfhe_ct* c, const aesfhe_pt* pt, aesfhe_ct** out) {
     API_BEGIN
     if (pt->level < c->level) throw_err(AESFHE_EARG, "plaintext level %d below ciphertext level %d", pt->level, c->level);
-    aesfhe_ct* r = ct_new(e, c->B, c->np, c->level);
+    CtPtr r = ct_new(e, c->B, c->np, c->level);
     hipLaunchKernelGGL(k_add_pt, ew_grid(e, c->level + 1, c->B * c->np), dim3(256), 0, e->stream, opnd(view_of(c), c->B), (const u64*)pt->d, out_of(r), c->np, e->q, e->logN);
     HIPC(hipGetLastError());
-    *out = r;
+    *out = r.release();
     API_END
 }
 
@@ -1965,11 +2013,11 @@ extern "C" int aesfhe_add_const(aesfhe_engine* e, const aesfhe_ct* c, double re,
     std::vector<double> ff;
     const_factors(e, A, Bc, c->level + 1, f, ff);
     u64* df = upload_small(e, f.data(), f.size());
-    aesfhe_ct* r = ct_new(e, c->B, c->np, c->level);
+    CtPtr r = ct_new(e, c->B, c->np, c->level);
     hipLaunchKernelGGL(k_add_const, ew_grid(e, c->level + 1, c->B * c->np), dim3(256), 0, e->stream, opnd(view_of(c), c->B), out_of(r), c->np, (const u64*)df, e->q, e->logN);
     HIPC(hipGetLastError());
     r->is_zero = c->is_zero && A == 0 && Bc == 0;
-    *out = r;
+    *out = r.release();
     API_END
 }
 
@@ -1978,13 +2026,12 @@ extern "C" int aesfhe_mul_pt(aesfhe_engine* e, const aesfhe_ct* c, const aesfhe_
     if (c->level < 1) throw_err(AESFHE_ELEVEL, "no level left for a plaintext multiplication");
     if (pt->level < c->level) throw_err(AESFHE_EARG, "plaintext level %d below ciphertext level %d", pt->level, c->level);
     if (c->is_zero) {
-        *out = ct_zero_new(e, c->B, c->np, c->level - 1);
+        *out = ct_zero_new(e, c->B, c->np, c->level - 1).release();
     } else {
-        aesfhe_ct* t = ct_new(e, c->B, c->np, c->level);
+        CtPtr t = ct_new(e, c->B, c->np, c->level);
         hipLaunchKernelGGL(k_mul_pt, ew_grid(e, c->level + 1, c->B * c->np), dim3(256), 0, e->stream, opnd(view_of(c), c->B), (const u64*)pt->d, out_of(t), c->np, e->q, e->qinv, e->logN);
         HIPC(hipGetLastError());
-        *out = rescale_view(e, view_of(t));
-        aesfhe_ct_free(t);
+        *out = rescale_view(e, view_of(t)).release();
     }
     API_END
 }
@@ -1995,12 +2042,11 @@ extern "C" int aesfhe_mul_const(aesfhe_engine* e, const aesfhe_ct* c, double re,
     double s = aesfhe_engine_mul_scale(e, c->level);
     int64_t A = llround(re * s), Bc = llround(im * s);
     if (c->is_zero || (A == 0 && Bc == 0)) {
-        *out = ct_zero_new(e, c->B, c->np, c->level - 1);
+        *out = ct_zero_new(e, c->B, c->np, c->level - 1).release();
     } else {
-        aesfhe_ct* t = ct_new(e, c->B, c->np, c->level);
-        mul_const_into(e, view_of(c), A, Bc, t, 0);
-        *out = rescale_view(e, view_of(t));
-        aesfhe_ct_free(t);
+        CtPtr t = ct_new(e, c->B, c->np, c->level);
+        mul_const_into(e, view_of(c), A, Bc, t.get(), 0);
+        *out = rescale_view(e, view_of(t)).release();
     }
     API_END
 }
@@ -2011,7 +2057,7 @@ extern "C" int aesfhe_mod_raise(aesfhe_engine* e, const aesfhe_ct* c, int32_t le
     API_BEGIN
     if (level < 0 || level > e->L) throw_err(AESFHE_EARG, "bad mod-raise level");
     const int N = e->N, P = c->B * c->np, nl = level + 1;
-    aesfhe_ct* r = ct_new(e, c->B, c->np, level);
+    CtPtr r = ct_new(e, c->B, c->np, level);
     if (c->is_zero) {
         HIPC(hipMemsetAsync(r->d, 0, r->bytes, e->stream));
         r->is_zero = 1;
@@ -2026,21 +2072,21 @@ extern "C" int aesfhe_mod_raise(aesfhe_engine* e, const aesfhe_ct* c, int32_t le
         Span so = span_s(r->d, (long)nl * N, nl, nl, 0, e->Lp1);
         ntt(e, so, so, P * nl, false);
     }
-    *out = r;
+    *out = r.release();
     API_END
 }
 
 // Multiplication by X^{N/2} (sign +1) or -X^{N/2}: every slot times i / -i, exact, no level.
 extern "C" int aesfhe_mul_i(aesfhe_engine* e, const aesfhe_ct* c, int32_t sign, aesfhe_ct** out) {
     API_BEGIN
-    aesfhe_ct* r = ct_new(e, c->B, c->np, c->level);
+    CtPtr r = ct_new(e, c->B, c->np, c->level);
     if (c->is_zero) {
         HIPC(hipMemsetAsync(r->d, 0, r->bytes, e->stream));
         r->is_zero = 1;
     } else {
-        mul_const_into(e, view_of(c), 0, sign >= 0 ? 1 : -1, r, 0);
+        mul_const_into(e, view_of(c), 0, sign >= 0 ? 1 : -1, r.get(), 0);
     }
-    *out = r;
+    *out = r.release();
     API_END
 }
 
@@ -2049,45 +2095,36 @@ extern "C" int aesfhe_mul_i(aesfhe_engine* e, const aesfhe_ct* c, int32_t sign, 
 extern "C" int aesfhe_dot_pt(aesfhe_engine* e, const aesfhe_ct* const* cts, const aesfhe_pt* const* pts, int32_t n, aesfhe_ct** out) {
     API_BEGIN
     if (n < 1 || n > 256) throw_err(AESFHE_EARG, "dot_pt needs 1..256 terms");
-    int l = cts[0]->level, B = 1, np = cts[0]->np;
-    for (int i = 0; i < n; i++) {
-        l = std::min(l, cts[i]->level);
-        B = std::max(B, cts[i]->B);
-        if (cts[i]->np != np) throw_err(AESFHE_EDEGREE, "dot_pt inputs should have the same number of polynomials");
-    }
-    for (int i = 0; i < n; i++) {
-        if (cts[i]->B != B && cts[i]->B != 1) throw_err(AESFHE_EARG, "batch mismatch");
+    const OperandScan sc = scan_operands(views_of(cts, n), kNpSame);
+    const int l = sc.level, B = sc.B, np = sc.np;
+    if (!sc.np_ok) throw_err(AESFHE_EDEGREE, "dot_pt inputs should have the same number of polynomials");
+    if (sc.mismatch) throw_err(AESFHE_EARG, "batch mismatch");
+    for (int i = 0; i < n; i++)
         if (pts[i]->level < l) throw_err(AESFHE_EARG, "plaintext level %d below ciphertext level %d", pts[i]->level, l);
-    }
     if (l < 1) throw_err(AESFHE_ELEVEL, "no level left for a plaintext dot product");
     const int nl = l + 1;
-    std::vector<std::unique_ptr<Aligned>> al;
-    std::vector<const u64*> pc, pp;
-    std::vector<long> sb;
+    std::vector<Aligned> al;
+    OperandTable tc, tp;  // the contributing ciphertexts (aligned to level l) and their plaintexts
     for (int i = 0; i < n; i++) {
         if (cts[i]->is_zero) continue;
-        al.emplace_back(new Aligned());
-        align_to(e, cts[i], l, *al.back());
-        const View& v = al.back()->v;
+        al.emplace_back();
+        align_to(e, cts[i], l, al.back());
+        const View& v = al.back().v;
         if (v.ps != (long)nl * e->N) throw_err(AESFHE_EARG, "dot_pt: non-compact view");
-        pc.push_back(v.d);
-        sb.push_back(v.B == 1 && B > 1 ? 0 : v.bs);
-        pp.push_back(pts[i]->d);
+        tc.add(v, B);
+        tp.ptr.push_back(pts[i]->d);
     }
-    if (pc.empty()) {
-        *out = ct_zero_new(e, B, np, l - 1);
+    if (tc.empty()) {
+        *out = ct_zero_new(e, B, np, l - 1).release();
     } else {
-        aesfhe_ct* acc = ct_new(e, B, np, l);
-        auto dpc = upload_small(e, pc.data(), pc.size());
-        auto dpp = upload_small(e, pp.data(), pp.size());
-        auto dsb = upload_small(e, sb.data(), sb.size());
+        CtPtr acc = ct_new(e, B, np, l);
+        const auto d = upload(e, {&tc, &tp}, OP_PTR | OP_BS);
         {
-            ProfScope ps_(e, FAM_EW, 8.0 * e->N * nl * (double)B * np * (pc.size() + 1), "dot_pt");
-            hipLaunchKernelGGL(k_dot_pt, ew_grid(e, nl, B * np), dim3(256), 0, e->stream, (const u64* const*)dpc, (const long*)dsb, (long)nl * e->N, (const u64* const*)dpp, (int)pc.size(), out_of(acc), np, e->q, e->qinv, e->logN);
+            ProfScope ps_(e, FAM_EW, 8.0 * e->N * nl * (double)B * np * (tc.size() + 1), "dot_pt");
+            hipLaunchKernelGGL(k_dot_pt, ew_grid(e, nl, B * np), dim3(256), 0, e->stream, d[0].ptr, d[0].bs, (long)nl * e->N, d[1].ptr, (int)tc.size(), out_of(acc), np, e->q, e->qinv, e->logN);
         }
         HIPC(hipGetLastError());
-        *out = rescale_view(e, view_of(acc));
-        aesfhe_ct_free(acc);
+        *out = rescale_view(e, view_of(acc)).release();
     }
     API_END
 }
@@ -2326,14 +2363,14 @@ static void ks_modup(aesfhe_engine* e, const u64* d, long dbs, int B, int l, u64
     // pass reads it into ext_j -- the in-place pass read and wrote the same lines; one digit's
     // extension of extra memory, not one per digit (with the ModDown conv pass out of place as
     // well: round +0.8 %, A/B/A/B/A on one box, profiles/r04/ab/oop/)
-    std::unique_ptr<Tmp> mu;  // only when some digit runs the unfused conversion (alpha > 1)
+    Tmp mu;  // only when some digit runs the unfused conversion (alpha > 1)
     bool any_wide = false;
     for (int j = 0; j < beta; j++) any_wide |= std::min((j + 1) * e->A, l + 1) - j * e->A > 1;
-    if (cols_only && any_wide && !fcols) mu.reset(new Tmp(e, (size_t)B * neN));
+    if (cols_only && any_wide && !fcols) mu = Tmp(e, (size_t)B * neN);
     for (int j = 0; j < beta; j++) {
         const int A = e->A, lo = j * A, hi = std::min(lo + A, l + 1), alpha = hi - lo;
         u64* exj = ext + (size_t)j * B * neN;
-        u64* muj = mu ? mu->p : exj;  // where ModUp writes (mu absent: every digit is one limb)
+        u64* muj = mu ? mu.p : exj;  // where ModUp writes (mu absent: every digit is one limb)
         if (cols_only && alpha == 1) {
             // one-limb digit: the conversion is x mod p_t (hat = hatinv = 1), formed in the column
             // pass's copy-in from the digit limb itself (no conversion launch, no write + read-back)
@@ -2486,7 +2523,7 @@ static void moddown_conv_cols(aesfhe_engine* e, const MdTabs& t, u64* acc, long 
 // are read: a caller that owns them releases them there, before conv2 is taken in the second
 // form.  `conv` of that form is read only by the column pass; it is the caller's to release.
 struct Conv2 {
-    std::unique_ptr<Tmp> conv, buf;  // released in reverse: buf, then conv
+    Tmp conv, buf;  // released in reverse: buf, then conv
 };
 template <typename F>
 static Conv2 moddown_conv2(aesfhe_engine* e, const MdTabs& t, u64* acc, long abs_, long acs, int B, int l, int r,
@@ -2495,17 +2532,17 @@ static Conv2 moddown_conv2(aesfhe_engine* e, const MdTabs& t, u64* acc, long abs
     const long kN = (long)(lk + 1) * e->N;
     Conv2 c;
     if (moddown_cols_ok(e, r)) {
-        c.buf.reset(new Tmp(e, (size_t)B * 2 * kN));
-        moddown_conv_cols(e, t, acc, abs_, acs, B, l, r, c.buf->p, rows_done);
+        c.buf = Tmp(e, (size_t)B * 2 * kN);
+        moddown_conv_cols(e, t, acc, abs_, acs, B, l, r, c.buf.p, rows_done);
         converted();
         return c;
     }
-    c.conv.reset(new Tmp(e, (size_t)B * 2 * kN));
-    moddown_conv(e, t, acc, abs_, acs, B, l, r, c.conv->p, rows_done);
+    c.conv = Tmp(e, (size_t)B * 2 * kN);
+    moddown_conv(e, t, acc, abs_, acs, B, l, r, c.conv.p, rows_done);
     converted();  // stream-ordered reuse of the dropped limbs from here on
-    c.buf.reset(new Tmp(e, (size_t)B * 2 * kN));
+    c.buf = Tmp(e, (size_t)B * 2 * kN);
     ProfScope ps(e, FAM_NTT, 8.0 * e->N * (double)total, "ntt_fwd_cols");
-    ntt_fwd_cols(e, span_s(c.conv->p, kN, lk + 1, lk + 1, 0, e->Lp1), span_s(c.buf->p, kN, lk + 1, lk + 1, 0, e->Lp1), total);
+    ntt_fwd_cols(e, span_s(c.conv.p, kN, lk + 1, lk + 1, 0, e->Lp1), span_s(c.buf.p, kN, lk + 1, lk + 1, 0, e->Lp1), total);
     return c;
 }
 
@@ -2525,7 +2562,7 @@ static void moddown_acc(aesfhe_engine* e, u64* acc, int B, int l, int r, Opnd fi
         // the row pass (credited half an NTT) plus the finish: acc read, output written (+ addend)
         ProfScope ps(e, FAM_NTT, 8.0 * N * (double)total * (3.0 + (fin_add.ptr ? 1.0 : 0.0)), "ntt_fwd_rows_fin");
         auto kern = N == 65536 ? k_nttf_fwd_rows_t<true, 256> : k_nttf_fwd_rows_t<true, 512>;
-        hipLaunchKernelGGL(kern, dim3(N / 4096, total), dim3(256), 0, e->stream, span_s(c.buf->p, kN, lk + 1, lk + 1, 0, e->Lp1),
+        hipLaunchKernelGGL(kern, dim3(N / 4096, total), dim3(256), 0, e->stream, span_s(c.buf.p, kN, lk + 1, lk + 1, 0, e->Lp1),
                            e->tabs(), f);
         HIPC(hipGetLastError());
         return;
@@ -2605,18 +2642,18 @@ static void ks_finish_fused(aesfhe_engine* e, const u64* d, long dbs, const u64*
     // switch at B = 32, l = 30 of memory never touched), addressed through a base pointer offset by
     // lk + 1 limbs so that limb t still sits at acc + t N
     const int nd = ne - (lk + 1);
-    std::unique_ptr<Tmp> own;
-    if (had_own) own.reset(new Tmp(e, (size_t)B * 2 * nd * N));
+    Tmp own;
+    if (had_own) own = Tmp(e, (size_t)B * 2 * nd * N);
     // (an address, not a C++ pointer into the block: only limbs >= lk + 1 are ever formed from it,
     // by the dropped limbs' launch and the ModDown conversion)
-    u64* acc = acc_in ? acc_in : reinterpret_cast<u64*>(reinterpret_cast<uintptr_t>(own->p) - (uintptr_t)(lk + 1) * N * sizeof(u64));
+    u64* acc = acc_in ? acc_in : reinterpret_cast<u64*>(reinterpret_cast<uintptr_t>(own.p) - (uintptr_t)(lk + 1) * N * sizeof(u64));
     const long abs_ = acc_in ? 2 * neN : 2L * nd * N, acs = acc_in ? neN : (long)nd * N;
     launch(lk + 1, nd, false, acc, abs_, acs, KsFin{});
     // the own block goes back once the dropped limbs are converted
     Conv2 c = moddown_conv2(e, t, acc, abs_, acs, B, l, r, true, [&] { own.reset(); });
     c.conv.reset();
     HIPC(hipGetLastError());
-    const KsFin kf{c.buf->p, 2 * kN, kN, o->d, 2 * kN, kN, t.dinvf, Opnd2{fin_add.ptr, fin_add.bs, fin_add.ps, fin_add.np}};
+    const KsFin kf{c.buf.p, 2 * kN, kN, o->d, 2 * kN, kN, t.dinvf, Opnd2{fin_add.ptr, fin_add.bs, fin_add.ps, fin_add.np}};
     // the kept limbs' accumulators exist only in acc_in (accumulating giants, read with accum);
     // with an own block -- released above, its memory perhaps conv2's by now -- FIN gets nullptr
     launch(0, lk + 1, true, had_own ? nullptr : acc, abs_, acs, kf);
@@ -2636,6 +2673,7 @@ static void ks_apply(aesfhe_engine* e, const u64* d, long dbs, const u64* ext, i
 
 static void keyswitch(aesfhe_engine* e, const u64* d, long dbs, int B, int l, const aesfhe_key* k,
                       Opnd addend, aesfhe_ct* o, int r = 0) {
+    check_key_digits(e, k, l);  // before the first block is taken and the first launch
     const long neN = (long)(l + 1 + e->K) * e->N;
     Tmp ext(e, (size_t)ks_beta(e, l) * B * neN);
     const bool fuse = fused_ntt(e);
@@ -2654,45 +2692,44 @@ static void keyswitch_prod(aesfhe_engine* e, const Opnd& pa, const Opnd& pb, int
                            aesfhe_ct* o, int r, const u64* fac = nullptr, const Opnd* pc = nullptr) {
     if (!fused_ntt(e) || r < 1 || pa.np != 2 || pb.np != 2 || !pa.ptr || !pb.ptr)
         throw_err(AESFHE_EARG, "product key switch outside the fused combined path");
+    check_key_digits(e, k, l);
     const long neN = (long)(l + 1 + e->K) * e->N;
     Tmp ext(e, (size_t)ks_beta(e, l) * B * neN);
     ks_modup(e, nullptr, 0, B, l, ext.p, true, &pa, &pb, fac);
     ks_finish_fused(e, nullptr, 0, ext.p, B, l, k, pa, true, r, Opnd{nullptr, 0, 0, 0}, o, &pb, fac, pc);
 }
 
-static aesfhe_ct* relin_ct(aesfhe_engine* e, const aesfhe_ct* c, const aesfhe_key* rlk) {
+static CtPtr relin_ct(aesfhe_engine* e, const aesfhe_ct* c, const aesfhe_key* rlk) {
     const int l = c->level;
-    aesfhe_ct* r = ct_new(e, c->B, 2, l);
+    check_key_digits(e, rlk, l);
+    CtPtr r = ct_new(e, c->B, 2, l);
     View v = view_of(c);
     Opnd add = opnd(v, c->B);
     add.np = 2;  // d0, d1 are the addends of outputs 0, 1
-    keyswitch(e, c->d + 2 * v.ps, v.bs, c->B, l, rlk, add, r);
+    keyswitch(e, c->d + 2 * v.ps, v.bs, c->B, l, rlk, add, r.get());
     return r;
 }
 
 // relinearisation of a 3-polynomial ciphertext fused with r rescales (r = 1, 2): level l - r
-static aesfhe_ct* relin_rescale(aesfhe_engine* e, const aesfhe_ct* c, const aesfhe_key* rlk, int r) {
+static CtPtr relin_rescale(aesfhe_engine* e, const aesfhe_ct* c, const aesfhe_key* rlk, int r) {
     const int l = c->level;
     if (r > 0 && e->K + r > kMdrMaxE) {  // no combined tables: separate steps
-        aesfhe_ct* x = relin_ct(e, c, rlk);
-        for (int i = 0; i < r; i++) {
-            aesfhe_ct* y = rescale_view(e, view_of(x));
-            aesfhe_ct_free(x);
-            x = y;
-        }
+        CtPtr x = relin_ct(e, c, rlk);
+        for (int i = 0; i < r; i++) x = rescale_view(e, view_of(x));
         return x;
     }
-    aesfhe_ct* out = ct_new(e, c->B, 2, l - r);
+    check_key_digits(e, rlk, l);
+    CtPtr out = ct_new(e, c->B, 2, l - r);
     View v = view_of(c);
     Opnd add = opnd(v, c->B);
     add.np = 2;
-    keyswitch(e, c->d + 2 * v.ps, v.bs, c->B, l, rlk, add, out, r);
+    keyswitch(e, c->d + 2 * v.ps, v.bs, c->B, l, rlk, add, out.get(), r);
     return out;
 }
 
-static aesfhe_ct* tensor_ct(aesfhe_engine* e, const View& a, const View& b, int B) {
+static CtPtr tensor_ct(aesfhe_engine* e, const View& a, const View& b, int B) {
     const int l = a.level;
-    aesfhe_ct* t = ct_new(e, B, 3, l);
+    CtPtr t = ct_new(e, B, 3, l);
     ProfScope ps(e, FAM_EW, 56.0 * e->N * (l + 1) * (double)B, "tensor");
     hipLaunchKernelGGL(k_tensor, ew_grid(e, l + 1, B), dim3(256), 0, e->stream, opnd(a, B), opnd(b, B), out_of(t), e->q, e->qinv, 0, e->logN);
     HIPC(hipGetLastError());
@@ -2705,12 +2742,12 @@ extern "C" int aesfhe_tensor(aesfhe_engine* e, const aesfhe_ct* a, const aesfhe_
     check_cyclic(a->B, b->B);
     int l = std::min(a->level, b->level), B = std::max(a->B, b->B);
     if (a->is_zero || b->is_zero) {
-        *out = ct_zero_new(e, B, 3, l);
+        *out = ct_zero_new(e, B, 3, l).release();
     } else {
         Aligned A, Bv;
         align_to(e, a, l, A);
         align_to(e, b, l, Bv);
-        *out = tensor_ct(e, A.v, Bv.v, B);
+        *out = tensor_ct(e, A.v, Bv.v, B).release();
     }
     API_END
 }
@@ -2719,40 +2756,34 @@ extern "C" int aesfhe_relinearize(aesfhe_engine* e, const aesfhe_ct* c, const ae
     API_BEGIN
     if (c->np != 3) throw_err(AESFHE_EDEGREE, "Input ciphertext should have 3 polynomials");
     if (!rlk || rlk->kind != 2) throw_err(AESFHE_EARG, "relinearize needs a relinearization key");
-    if (c->is_zero) *out = ct_zero_new(e, c->B, 2, c->level);
-    else *out = relin_ct(e, c, rlk);
+    if (c->is_zero) *out = ct_zero_new(e, c->B, 2, c->level).release();
+    else *out = relin_ct(e, c, rlk).release();
     API_END
 }
 
-static aesfhe_ct* mul_ct(aesfhe_engine* e, const aesfhe_ct* a, const aesfhe_ct* b, const aesfhe_key* rlk) {
+static CtPtr mul_ct(aesfhe_engine* e, const aesfhe_ct* a, const aesfhe_ct* b, const aesfhe_key* rlk) {
     check_cyclic(a->B, b->B);
     int l = std::min(a->level, b->level), B = std::max(a->B, b->B);
     if (l < 1) throw_err(AESFHE_ELEVEL, "no level left for a ciphertext multiplication");
     if (a->is_zero || b->is_zero) return ct_zero_new(e, B, 2, l - 1);
+    check_key_digits(e, rlk, l);
     Aligned A, Bv;
     align_to(e, a, l, A);
     align_to(e, b, l, Bv);
     if (fused_ntt(e) && e->K + 1 <= kMdrMaxE) {
-        aesfhe_ct* r = ct_new(e, B, 2, l - 1);
-        try {
-            keyswitch_prod(e, opnd(A.v, B), opnd(Bv.v, B), B, l, rlk, r, 1);
-        } catch (...) {
-            aesfhe_ct_free(r);
-            throw;
-        }
+        CtPtr r = ct_new(e, B, 2, l - 1);
+        keyswitch_prod(e, opnd(A.v, B), opnd(Bv.v, B), B, l, rlk, r.get(), 1);
         return r;
     }
-    aesfhe_ct* t = tensor_ct(e, A.v, Bv.v, B);
-    aesfhe_ct* r = relin_rescale(e, t, rlk, 1);
-    aesfhe_ct_free(t);
-    return r;
+    CtPtr t = tensor_ct(e, A.v, Bv.v, B);
+    return relin_rescale(e, t.get(), rlk, 1);
 }
 
 extern "C" int aesfhe_mul(aesfhe_engine* e, const aesfhe_ct* a, const aesfhe_ct* b, const aesfhe_key* rlk, aesfhe_ct** out) {
     API_BEGIN
     if (!rlk || rlk->kind != 2) throw_err(AESFHE_EARG, "multiply needs a relinearization key");
     if (a->np != 2 || b->np != 2) throw_err(AESFHE_EDEGREE, "multiply inputs should have 2 polynomials");
-    *out = mul_ct(e, a, b, rlk);
+    *out = mul_ct(e, a, b, rlk).release();
     API_END
 }
 
@@ -2767,14 +2798,16 @@ extern "C" int aesfhe_mul_fma(aesfhe_engine* e, const aesfhe_ct* a, const aesfhe
     if (a->np != 2 || b->np != 2) throw_err(AESFHE_EDEGREE, "multiply inputs should have 2 polynomials");
     const int l = std::min(a->level, b->level);
     if (l < 1) throw_err(AESFHE_ELEVEL, "no level left for a ciphertext multiplication");
-    int B = std::max(a->B, b->B);
     if (c) {
         if (c->np != 2) throw_err(AESFHE_EDEGREE, "fma addend should have 2 polynomials");
         if (c->level < l) throw_err(AESFHE_ELEVEL, "fma addend level %d below the product level %d", c->level, l);
-        B = std::max(B, c->B);
     }
-    if ((a->B != B && a->B != 1) || (b->B != B && b->B != 1) || (c && c->B != B && c->B != 1))
-        throw_err(AESFHE_EARG, "batch mismatch");
+    std::vector<Operand> ops{view_of(a), view_of(b)};
+    if (c) ops.push_back(view_of(c));
+    const OperandScan sc = scan_operands(ops, kNpTwo);
+    if (sc.mismatch) throw_err(AESFHE_EARG, "batch mismatch");
+    const int B = sc.B;
+    check_key_digits(e, rlk, l);  // every path below relinearises at level l
     Aligned A, Bv;
     const bool prod = !a->is_zero && !b->is_zero;
     if (prod) {
@@ -2795,31 +2828,20 @@ extern "C" int aesfhe_mul_fma(aesfhe_engine* e, const aesfhe_ct* a, const aesfhe
     u64* dfac = upload_small(e, fac.data(), fac.size());
     const Opnd none{nullptr, 0, 0, 0};
     if (prod && fused_ntt(e) && e->K + 1 <= kMdrMaxE) {  // tensor-free (keyswitch_prod with the fma factors)
-        aesfhe_ct* r = ct_new(e, B, 2, l - 1);
-        try {
-            const Opnd oc = hasc ? opnd(trunc_view(c, l), B) : none;
-            keyswitch_prod(e, opnd(A.v, B), opnd(Bv.v, B), B, l, rlk, r, 1, dfac, &oc);
-        } catch (...) {
-            aesfhe_ct_free(r);
-            throw;
-        }
-        *out = r;
+        CtPtr r = ct_new(e, B, 2, l - 1);
+        const Opnd oc = hasc ? opnd(trunc_view(c, l), B) : none;
+        keyswitch_prod(e, opnd(A.v, B), opnd(Bv.v, B), B, l, rlk, r.get(), 1, dfac, &oc);
+        *out = r.release();
         return AESFHE_OK;
     }
-    aesfhe_ct* t = ct_new(e, B, 3, l);
+    CtPtr t = ct_new(e, B, 3, l);
     {
         ProfScope ps(e, FAM_EW, 72.0 * e->N * (l + 1) * (double)B, "tensor_fma");
         hipLaunchKernelGGL(k_tensor_fma, ew_grid(e, l + 1, B), dim3(256), 0, e->stream, prod ? opnd(A.v, B) : none, prod ? opnd(Bv.v, B) : none,
                            hasc ? opnd(trunc_view(c, l), B) : none, out_of(t), (const u64*)dfac, e->q, e->qinv, e->logN);
     }
     HIPC(hipGetLastError());
-    try {
-        *out = relin_rescale(e, t, rlk, 1);
-    } catch (...) {
-        aesfhe_ct_free(t);
-        throw;
-    }
-    aesfhe_ct_free(t);
+    *out = relin_rescale(e, t.get(), rlk, 1).release();
     API_END
 }
 
@@ -2829,20 +2851,20 @@ extern "C" int aesfhe_galois(aesfhe_engine* e, const aesfhe_ct* c, const aesfhe_
     if (c->np != 2) throw_err(AESFHE_EDEGREE, "Input ciphertext should have 2 polynomials");
     const int N = e->N, l = c->level;
     if (c->is_zero) {
-        *out = ct_zero_new(e, c->B, 2, l);
+        *out = ct_zero_new(e, c->B, 2, l).release();
     } else {
+        check_key_digits(e, gk, l);
         // permute both polynomials into a temporary ct, then key-switch poly 1
-        aesfhe_ct* p = ct_new(e, c->B, 2, l);
+        CtPtr p = ct_new(e, c->B, 2, l);
         Span src = span_s(c->d, (long)(l + 1) * N, l + 1, l + 1, 0, e->Lp1), dst = span_s(p->d, (long)(l + 1) * N, l + 1, l + 1, 0, e->Lp1);
         hipLaunchKernelGGL(k_galois, dim3(N / 256, c->B * 2 * (l + 1)), dim3(256), 0, e->stream, src, dst, (u64)gk->galois, e->logN, e->Lp1);
         HIPC(hipGetLastError());
-        aesfhe_ct* r = ct_new(e, c->B, 2, l);
+        CtPtr r = ct_new(e, c->B, 2, l);
         View pv = view_of(p);
         Opnd add = opnd(pv, c->B);
         add.np = 1;  // only output 0 gets sigma(c0)
-        keyswitch(e, p->d + pv.ps, pv.bs, c->B, l, gk, add, r);
-        aesfhe_ct_free(p);
-        *out = r;
+        keyswitch(e, p->d + pv.ps, pv.bs, c->B, l, gk, add, r.get());
+        *out = r.release();
     }
     API_END
 }
@@ -2858,32 +2880,28 @@ extern "C" int aesfhe_rotate_hoisted(aesfhe_engine* e, const aesfhe_ct* c, const
     if (c->np != 2) throw_err(AESFHE_EDEGREE, "Input ciphertext should have 2 polynomials");
     const int N = e->N, l = c->level, B = c->B;
     for (int i = 0; i < n; i++) outs[i] = nullptr;
-    try {
-        if (c->is_zero) {
-            for (int i = 0; i < n; i++) outs[i] = ct_zero_new(e, B, 2, l);
-        } else {
-            const long neN = (long)(l + 1 + e->K) * N;
-            View cv = view_of(c);
-            const u64* c1 = c->d + cv.ps;
-            Tmp ext(e, (size_t)ks_beta(e, l) * B * neN);
-            ks_modup(e, c1, cv.bs, B, l, ext.p);
-            for (int i = 0; i < n; i++) {
-                aesfhe_ct* r = ct_new(e, B, 2, l);
-                Opnd add = opnd(cv, B);
-                add.np = 1;  // output 0 gets c0
-                ks_apply(e, c1, cv.bs, ext.p, B, l, keys[i], add, r, 0);
-                aesfhe_ct* o = ct_new(e, B, 2, l);
-                Span src = span_s(r->d, (long)(l + 1) * N, l + 1, l + 1, 0, e->Lp1), dst = span_s(o->d, (long)(l + 1) * N, l + 1, l + 1, 0, e->Lp1);
-                hipLaunchKernelGGL(k_galois, dim3(N / 256, B * 2 * (l + 1)), dim3(256), 0, e->stream, src, dst, (u64)keys[i]->galois, e->logN, e->Lp1);
-                HIPC(hipGetLastError());
-                aesfhe_ct_free(r);
-                outs[i] = o;
-            }
+    std::vector<CtPtr> res(n);
+    if (c->is_zero) {
+        for (int i = 0; i < n; i++) res[i] = ct_zero_new(e, B, 2, l);
+    } else {
+        for (int i = 0; i < n; i++) check_key_digits(e, keys[i], l);
+        const long neN = (long)(l + 1 + e->K) * N;
+        View cv = view_of(c);
+        const u64* c1 = c->d + cv.ps;
+        Tmp ext(e, (size_t)ks_beta(e, l) * B * neN);
+        ks_modup(e, c1, cv.bs, B, l, ext.p);
+        for (int i = 0; i < n; i++) {
+            CtPtr r = ct_new(e, B, 2, l);
+            Opnd add = opnd(cv, B);
+            add.np = 1;  // output 0 gets c0
+            ks_apply(e, c1, cv.bs, ext.p, B, l, keys[i], add, r.get(), 0);
+            res[i] = ct_new(e, B, 2, l);
+            Span src = span_s(r->d, (long)(l + 1) * N, l + 1, l + 1, 0, e->Lp1), dst = span_s(res[i]->d, (long)(l + 1) * N, l + 1, l + 1, 0, e->Lp1);
+            hipLaunchKernelGGL(k_galois, dim3(N / 256, B * 2 * (l + 1)), dim3(256), 0, e->stream, src, dst, (u64)keys[i]->galois, e->logN, e->Lp1);
+            HIPC(hipGetLastError());
         }
-    } catch (...) {
-        for (int i = 0; i < n; i++) aesfhe_ct_free(outs[i]), outs[i] = nullptr;
-        throw;
     }
+    release_all(res, outs);
     API_END
 }
 
@@ -2906,6 +2924,7 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
         if (gkeys[j] && gkeys[j]->kind != 3) throw_err(AESFHE_EARG, "giant steps need galois keys");
         tot += nterm[j];
     }
+    for (int j = 0; j < ng && !c->is_zero; j++) check_key_digits(e, gkeys[j], l - 1);  // the giants switch at level l - 1
     for (int i = 0; i < nb; i++) {
         if (bkeys[i] && bkeys[i]->kind != 5) throw_err(AESFHE_EARG, "baby steps need hoisted rotation keys");
         check_key_digits(e, bkeys[i], l);
@@ -2915,7 +2934,7 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
         if (!pts[t] || !pts[t]->ext || pts[t]->level != l) throw_err(AESFHE_EARG, "linear_bsgs needs Q u P plaintexts at the input level");
     }
     if (c->is_zero) {
-        *out = ct_zero_new(e, B, 2, l - 1);
+        *out = ct_zero_new(e, B, 2, l - 1).release();
         return 0;
     }
     View cv = view_of(c);
@@ -2923,35 +2942,35 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
     Opnd c0 = opnd(cv, B);
     c0.np = 1;  // P * c0 joins accumulator 0 only
     // 1. babies in Q_l u P
-    std::vector<std::unique_ptr<Tmp>> E;
+    std::vector<Tmp> E;
     bool any_key = false;
     for (int i = 0; i < nb; i++) any_key |= bkeys[i] != nullptr;
     // fused: the babies are formed inside the term sums (k_bsgs_terms) from the extension and the
     // keys, never written
     bool fused_terms = true;  // k_bsgs_terms peels a key-less (identity) baby at index 0 only
     for (int i = 1; i < nb; i++) fused_terms &= bkeys[i] != nullptr;
-    std::unique_ptr<Tmp> ext_keep;
+    Tmp ext_keep;
     if (fused_terms && any_key) {
-        ext_keep.reset(new Tmp(e, (size_t)ks_beta(e, l) * B * neN));
-        ks_modup(e, c1, cv.bs, B, l, ext_keep->p);
+        ext_keep = Tmp(e, (size_t)ks_beta(e, l) * B * neN);
+        ks_modup(e, c1, cv.bs, B, l, ext_keep.p);
     }
     if (!fused_terms) {
-        std::unique_ptr<Tmp> ext;
+        Tmp ext;
         if (any_key) {
-            ext.reset(new Tmp(e, (size_t)ks_beta(e, l) * B * neN));
-            ks_modup(e, c1, cv.bs, B, l, ext->p);
+            ext = Tmp(e, (size_t)ks_beta(e, l) * B * neN);
+            ks_modup(e, c1, cv.bs, B, l, ext.p);
         }
         std::vector<const u64*> kd;
         std::vector<u64*> ko;
         for (int i = 0; i < nb; i++) {
-            E.emplace_back(new Tmp(e, (size_t)B * 2 * neN));
+            E.emplace_back(e, (size_t)B * 2 * neN);
             if (!bkeys[i]) {
-                hipLaunchKernelGGL(k_scale_p_ext, dim3(N / 256, ne, B * 2), dim3(256), 0, e->stream, opnd(cv, B), E.back()->p, l, ne, e->q, e->qinv, (const double*)e->pmodf, e->Lp1, e->logN);
+                hipLaunchKernelGGL(k_scale_p_ext, dim3(N / 256, ne, B * 2), dim3(256), 0, e->stream, opnd(cv, B), E.back().p, l, ne, e->q, e->qinv, (const double*)e->pmodf, e->Lp1, e->logN);
                 HIPC(hipGetLastError());
                 continue;
             }
             kd.push_back((const u64*)bkeys[i]->d);
-            ko.push_back(E.back()->p);
+            ko.push_back(E.back().p);
         }
         if (!kd.empty()) {
             // every keyed baby's inner product in one launch (the extension read once from HBM);
@@ -2961,15 +2980,15 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
             auto dko = upload_small(e, ko.data(), ko.size());
             ProfScope ps(e, FAM_KS, 8.0 * N * (double)ne * (beta * B + kd.size() * (2.0 * beta + 2.0 * B)), "ks_inner_multi");
             auto inner = beta <= 4 ? k_ks_inner_multi<4, 4> : beta <= 8 ? k_ks_inner_multi<8, 2> : k_ks_inner_multi<12, 1>;
-            hipLaunchKernelGGL(inner, dim3(N / 256, ne, 1), dim3(256), 0, e->stream, c1, cv.bs, (const u64*)ext->p, neN, (long)B * neN, (const u64* const*)dk, (int)kd.size(), 2L * e->np * N, (long)e->np * N, (u64* const*)dko, 2 * neN, neN, B, beta, e->A, l, e->q, e->qinv, e->Lp1, c0, (const double*)e->pmodf, e->logN);
+            hipLaunchKernelGGL(inner, dim3(N / 256, ne, 1), dim3(256), 0, e->stream, c1, cv.bs, (const u64*)ext.p, neN, (long)B * neN, (const u64* const*)dk, (int)kd.size(), 2L * e->np * N, (long)e->np * N, (u64* const*)dko, 2 * neN, neN, B, beta, e->A, l, e->q, e->qinv, e->Lp1, c0, (const double*)e->pmodf, e->logN);
             HIPC(hipGetLastError());
         }
     }
     // 2. giant parts: sum of plaintext products in Q_l u P (every giant in one pass over the
     // babies, kGM at a time), ModDown fused with the rescale
-    std::vector<aesfhe_ct*> parts(ng, nullptr);
-    aesfhe_ct* sumq = nullptr;
-    try {
+    std::vector<CtPtr> parts(ng);
+    CtPtr sumq;
+    {
         constexpr int kGM = 8;
         // the term tables, validated and sized on the host (bsgs_plan.h, ASan-tested)
         std::vector<BsgsChunk> plan;
@@ -2982,7 +3001,7 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
         std::vector<const u64*> ep(nb);
         std::vector<u64> gal(nb, 0);
         for (int i = 0; i < nb; i++) {
-            ep[i] = fused_terms ? (bkeys[i] ? (const u64*)bkeys[i]->d : nullptr) : E[i]->p;  // fused: the baby's key
+            ep[i] = fused_terms ? (bkeys[i] ? (const u64*)bkeys[i]->d : nullptr) : E[i].p;  // fused: the baby's key
             gal[i] = bkeys[i] ? bkeys[i]->galois : 0;
         }
         auto dep = upload_small(e, ep.data(), ep.size());
@@ -2992,11 +3011,11 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
         for (const BsgsChunk& ch : plan) {
             const int j0 = ch.j0, gn = ch.gn;
             const double terms = ch.terms;
-            std::vector<std::unique_ptr<Tmp>> S;
+            std::vector<Tmp> S;
             std::vector<u64*> so;
             for (int j = 0; j < gn; j++) {
-                S.emplace_back(new Tmp(e, (size_t)B * 2 * neN));
-                so.push_back(S.back()->p);
+                S.emplace_back(e, (size_t)B * 2 * neN);
+                so.push_back(S.back().p);
             }
             auto dpt = upload_small(e, ch.pt.data(), ch.pt.size());
             auto dso = upload_small(e, so.data(), so.size());
@@ -3007,7 +3026,7 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
                 const int beta = ks_beta(e, l);
                 ProfScope ps_(e, FAM_EW, 8.0 * N * ne * ((double)B * (beta + 2 + 2.0 * gn) + 2.0 * beta * nb + terms),
                               "bsgs_terms");
-                const u64* ex = ext_keep ? (const u64*)ext_keep->p : (const u64*)c->d;  // no keyed baby: never read
+                const u64* ex = ext_keep ? (const u64*)ext_keep.p : (const u64*)c->d;  // no keyed baby: never read
                 // accumulator pairs GM >= gn, digit words BM = beta exactly, batch block BB (registers
                 // 2 BB GM doubles), PB babies' loads in flight together: tools/bsgs_bench.hip timed
                 // <2, 3, 4, 2> at 3.07 ms against 3.75 (PB 1), 3.32 (BB 8), 4.00 (PB 3); <4, 3, 4, 2>
@@ -3034,7 +3053,7 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
             HIPC(hipGetLastError());
             for (int j = 0; j < gn; j++) {
                 parts[j0 + j] = ct_new(e, B, 2, l - 1);
-                moddown_acc(e, S[j]->p, B, l, 1, Opnd{nullptr, 0, 0, 0}, parts[j0 + j]);
+                moddown_acc(e, S[j].p, B, l, 1, Opnd{nullptr, 0, 0, 0}, parts[j0 + j].get());
             }
         }
         E.clear();
@@ -3042,23 +3061,21 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
         // 3. giants: key switches of sigma_j(part_j) summed in Q_{l-1} u P, one ModDown
         const int l2 = l - 1, ne2 = l2 + 1 + K;
         const long ne2N = (long)ne2 * N, l2N = (long)(l2 + 1) * N;
-        std::unique_ptr<Tmp> accg;
+        Tmp accg;
         const bool fuse = fused_ntt(e);
         int last = -1;  // the last keyed giant: its key switch carries the ModDown (fused_ntt engines)
         for (int j = 0; j < ng; j++)
             if (gkeys[j]) last = j;
-        aesfhe_ct* fused_out = nullptr;
+        bool fused_out = false;
         for (int j = 0; j < ng; j++) {
             if (!gkeys[j]) {
                 if (!sumq) {
-                    sumq = parts[j];
-                    parts[j] = nullptr;
+                    sumq = std::move(parts[j]);
                 } else {
-                    aesfhe_ct* s2 = ct_new(e, B, 2, l2);
+                    CtPtr s2 = ct_new(e, B, 2, l2);
                     hipLaunchKernelGGL(k_addsub, ew_grid(e, l2 + 1, B * 2), dim3(256), 0, e->stream, opnd(view_of(sumq), B), opnd(view_of(parts[j]), B), out_of(s2), 2, e->q, 0, e->logN);
                     HIPC(hipGetLastError());
-                    aesfhe_ct_free(sumq);
-                    sumq = s2;
+                    sumq = std::move(s2);
                 }
                 continue;
             }
@@ -3070,39 +3087,29 @@ extern "C" int aesfhe_linear_bsgs(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
             Tmp ext(e, (size_t)ks_beta(e, l2) * B * ne2N);
             ks_modup(e, sg.p + l2N, 2 * l2N, B, l2, ext.p, fuse);
             const bool first = !accg;
-            if (first) accg.reset(new Tmp(e, (size_t)B * 2 * ne2N));
+            if (first) accg = Tmp(e, (size_t)B * 2 * ne2N);
             if (fuse && j == last) {
                 // the sum's ModDown by P fused into this key switch's row pass (ks_finish_fused):
                 // the kept limbs' accumulators are finished in registers, with sumq added
-                fused_out = ct_new(e, B, 2, l2);
+                CtPtr fo = ct_new(e, B, 2, l2);
                 Opnd add = sumq ? opnd(view_of(sumq), B) : Opnd{nullptr, 0, 0, 0};
-                try {
-                    ks_finish_fused(e, sg.p + l2N, 2 * l2N, ext.p, B, l2, gkeys[j], s0, true, 0, add, fused_out,
-                                    nullptr, nullptr, nullptr, accg->p, !first);
-                } catch (...) {
-                    aesfhe_ct_free(fused_out);
-                    throw;
-                }
-                if (sumq) aesfhe_ct_free(sumq);
-                sumq = fused_out;
+                ks_finish_fused(e, sg.p + l2N, 2 * l2N, ext.p, B, l2, gkeys[j], s0, true, 0, add, fo.get(),
+                                nullptr, nullptr, nullptr, accg.p, !first);
+                sumq = std::move(fo);
+                fused_out = true;
                 continue;
             }
-            ks_inner_acc(e, sg.p + l2N, 2 * l2N, ext.p, B, l2, gkeys[j], s0, true, accg->p, fuse, !first);
+            ks_inner_acc(e, sg.p + l2N, 2 * l2N, ext.p, B, l2, gkeys[j], s0, true, accg.p, fuse, !first);
         }
         if (accg && !fused_out) {
-            aesfhe_ct* r = ct_new(e, B, 2, l2);
+            CtPtr r = ct_new(e, B, 2, l2);
             Opnd add = sumq ? opnd(view_of(sumq), B) : Opnd{nullptr, 0, 0, 0};
-            moddown_acc(e, accg->p, B, l2, 0, add, r);
-            if (sumq) aesfhe_ct_free(sumq);
-            sumq = r;
+            moddown_acc(e, accg.p, B, l2, 0, add, r.get());
+            sumq = std::move(r);
         }
-    } catch (...) {
-        for (auto* p : parts) aesfhe_ct_free(p);
-        if (sumq) aesfhe_ct_free(sumq);
-        throw;
     }
-    for (auto* p : parts) aesfhe_ct_free(p);
-    *out = sumq;
+    for (CtPtr& p : parts) p.reset();
+    *out = sumq.release();
     API_END
 }
 
@@ -3126,57 +3133,50 @@ static void power_basis_batched(aesfhe_engine* e, const aesfhe_ct* c, int d, con
         return View{p, B, 2, lv, ps, 2 * ps, false};
     };
     for (int k = 0; k < d; k++) outs[k] = nullptr;
-    std::vector<aesfhe_ct*> lower, nxt;  // lower halves of O_j (temporaries), parts of O_{j+1}
-    auto drop = [&](std::vector<aesfhe_ct*>& v) {
-        for (auto* p : v) aesfhe_ct_free(p);
+    std::vector<CtPtr> res(d), lower, nxt;  // the powers; lower halves of O_j (temporaries), parts of O_{j+1}
+    auto drop = [&](std::vector<CtPtr>& v) {
+        for (CtPtr& p : v) p.reset();
         v.clear();
     };
-    try {
-        outs[0] = ct_new(e, 1, 2, l0);
-        HIPC(hipMemcpyAsync(outs[0]->d, c->d, outs[0]->bytes, hipMemcpyDeviceToDevice, e->stream));
-        const u64* opd = c->d;  // slot 0 of O_j (depth 0: x itself)
-        for (int j = 0; j < need; j++) {
-            const int S = 1 << j, lv = l0 - j, m = std::min(2 * S, d) - S;
-            const size_t pw = (size_t)2 * (lv + 1) * N;
-            const View va = pview(opd + (size_t)(S - 1) * pw, 1, lv), vb = pview(opd, m, lv);
-            if (d > 2 * S) {  // another depth follows: the products fill the upper half of O_{j+1}
-                nxt = ct_split_batch(e, ct_new(e, 2 * S, 2, lv - 1), 2 * S);
-                aesfhe_ct alias{e, S, 2, lv - 1, 0, nxt[S]->d, 0};
-                keyswitch_prod(e, opnd(va, S), opnd(vb, S), S, lv, rlk, &alias, 1);
-                for (int t = 0; t < S; t++) outs[S + t] = nxt[S + t], nxt[S + t] = nullptr;
-                nxt.resize(S);
-                drop(lower);  // O_j's level-downed half: its last reader is enqueued
-                // O_{j+1}'s lower half: x^{1..min(S, m_{j+1})} at level lv - 1, per source depth i
-                // (x^{lo..hi} at level l0 - i) one batched level-down into the block
-                const int mnext = std::min(4 * S, d) - 2 * S;
-                for (int i = 0; i <= j; i++) {
-                    const int lo = i ? (1 << (i - 1)) + 1 : 1, hi = std::min(1 << i, mnext);
-                    if (hi < lo) break;
-                    const int sl = l0 - i;
-                    rescale_view(e, truncated(pview(outs[lo - 1]->d, hi - lo + 1, sl), lv), level_down_const(e, sl, lv - 1),
-                                 nxt[lo - 1]->d);
-                }
-                lower.swap(nxt);
-                opd = lower[0]->d;
-            } else {  // last depth: the m outputs as one block, split
-                aesfhe_ct* r = ct_new(e, m, 2, lv - 1);
-                try {
-                    keyswitch_prod(e, opnd(va, m), opnd(vb, m), m, lv, rlk, r, 1);
-                } catch (...) {
-                    aesfhe_ct_free(r);
-                    throw;
-                }
-                std::vector<aesfhe_ct*> parts = m > 1 ? ct_split_batch(e, r, m) : std::vector<aesfhe_ct*>{r};
-                for (int t = 0; t < m; t++) outs[S + t] = parts[t];
-                drop(lower);
+    res[0] = ct_new(e, 1, 2, l0);
+    HIPC(hipMemcpyAsync(res[0]->d, c->d, res[0]->bytes, hipMemcpyDeviceToDevice, e->stream));
+    const u64* opd = c->d;  // slot 0 of O_j (depth 0: x itself)
+    for (int j = 0; j < need; j++) {
+        const int S = 1 << j, lv = l0 - j, m = std::min(2 * S, d) - S;
+        const size_t pw = (size_t)2 * (lv + 1) * N;
+        const View va = pview(opd + (size_t)(S - 1) * pw, 1, lv), vb = pview(opd, m, lv);
+        if (d > 2 * S) {  // another depth follows: the products fill the upper half of O_{j+1}
+            nxt = ct_split_batch(e, ct_new(e, 2 * S, 2, lv - 1), 2 * S);
+            aesfhe_ct alias{e, S, 2, lv - 1, 0, nxt[S]->d, 0};
+            keyswitch_prod(e, opnd(va, S), opnd(vb, S), S, lv, rlk, &alias, 1);
+            for (int t = 0; t < S; t++) res[S + t] = std::move(nxt[S + t]);
+            nxt.resize(S);
+            drop(lower);  // O_j's level-downed half: its last reader is enqueued
+            // O_{j+1}'s lower half: x^{1..min(S, m_{j+1})} at level lv - 1, per source depth i
+            // (x^{lo..hi} at level l0 - i) one batched level-down into the block
+            const int mnext = std::min(4 * S, d) - 2 * S;
+            for (int i = 0; i <= j; i++) {
+                const int lo = i ? (1 << (i - 1)) + 1 : 1, hi = std::min(1 << i, mnext);
+                if (hi < lo) break;
+                const int sl = l0 - i;
+                rescale_view(e, truncated(pview(res[lo - 1]->d, hi - lo + 1, sl), lv), level_down_const(e, sl, lv - 1),
+                             nxt[lo - 1]->d);
             }
+            lower.swap(nxt);
+            opd = lower[0]->d;
+        } else {  // last depth: the m outputs as one block, split
+            CtPtr r = ct_new(e, m, 2, lv - 1);
+            keyswitch_prod(e, opnd(va, m), opnd(vb, m), m, lv, rlk, r.get(), 1);
+            if (m > 1) {
+                std::vector<CtPtr> parts = ct_split_batch(e, std::move(r), m);
+                for (int t = 0; t < m; t++) res[S + t] = std::move(parts[t]);
+            } else {
+                res[S] = std::move(r);
+            }
+            drop(lower);
         }
-    } catch (...) {
-        drop(lower);
-        drop(nxt);
-        for (int k = 0; k < d; k++) aesfhe_ct_free(outs[k]), outs[k] = nullptr;
-        throw;
     }
+    release_all(res, outs);
 }
 
 extern "C" int aesfhe_power_basis(aesfhe_engine* e, const aesfhe_ct* c, int32_t d, const aesfhe_key* rlk, aesfhe_ct** outs) {
@@ -3191,94 +3191,72 @@ extern "C" int aesfhe_power_basis(aesfhe_engine* e, const aesfhe_ct* c, int32_t 
         power_basis_batched(e, c, d, rlk, outs);
         return AESFHE_OK;
     }
-    std::vector<aesfhe_ct*> pw(d + 1, nullptr);
+    std::vector<CtPtr> pw(d + 1);
     // memo of level-downed powers: (k, level) -> ct
-    std::map<std::pair<int, int>, aesfhe_ct*> memo;
-    try {
-        aesfhe_ct_copy(e, c, &pw[1]);
-        auto at_level = [&](int k, int lv) -> aesfhe_ct* {
-            if (pw[k]->level == lv) return pw[k];
-            auto key = std::make_pair(k, lv);
-            auto it = memo.find(key);
-            if (it != memo.end()) return it->second;
-            aesfhe_ct* x = level_down_view(e, view_of(pw[k]), lv);
-            memo[key] = x;
-            return x;
-        };
-        for (int k = 2; k <= d; k++) {
-            int hi = 1;
-            while (hi * 2 <= k) hi *= 2;
-            int k1 = (hi == k) ? k / 2 : hi, k2 = (hi == k) ? k / 2 : k - hi;
-            int lv = std::min(pw[k1]->level, pw[k2]->level);
-            pw[k] = mul_ct(e, at_level(k1, lv), at_level(k2, lv), rlk);
-        }
-    } catch (...) {
-        for (auto* p : pw) aesfhe_ct_free(p);
-        for (auto& kv : memo) aesfhe_ct_free(kv.second);
-        throw;
+    std::map<std::pair<int, int>, CtPtr> memo;
+    pw[1] = ct_copy_new(e, c);
+    auto at_level = [&](int k, int lv) -> const aesfhe_ct* {
+        if (pw[k]->level == lv) return pw[k].get();
+        CtPtr& x = memo[std::make_pair(k, lv)];
+        if (!x) x = level_down_view(e, view_of(pw[k]), lv);
+        return x.get();
+    };
+    for (int k = 2; k <= d; k++) {
+        int hi = 1;
+        while (hi * 2 <= k) hi *= 2;
+        int k1 = (hi == k) ? k / 2 : hi, k2 = (hi == k) ? k / 2 : k - hi;
+        int lv = std::min(pw[k1]->level, pw[k2]->level);
+        pw[k] = mul_ct(e, at_level(k1, lv), at_level(k2, lv), rlk);
     }
-    for (auto& kv : memo) aesfhe_ct_free(kv.second);
-    for (int k = 1; k <= d; k++) outs[k - 1] = pw[k];
+    for (auto& kv : memo) kv.second.reset();  // in key order, before the powers leave
+    for (int k = 1; k <= d; k++) outs[k - 1] = pw[k].release();
     API_END
+}
+
+// the inputs of a linear combination: lowest level (>= 1), largest batch, most polynomials
+static OperandScan lincomb_scan(const aesfhe_ct* const* cts, int n) {
+    const OperandScan sc = scan_operands(views_of(cts, n), kNpMax);
+    if (sc.mismatch) throw_err(AESFHE_EARG, "batch mismatch");
+    if (sc.level < 1) throw_err(AESFHE_ELEVEL, "no level left for a linear combination");
+    return sc;
 }
 
 extern "C" int aesfhe_lincomb(aesfhe_engine* e, const aesfhe_ct* const* cts, int32_t n, const double* re, const double* im, aesfhe_ct** out) {
     API_BEGIN
     if (n < 1) throw_err(AESFHE_EARG, "empty linear combination");
     if (n > 4096) throw_err(AESFHE_EARG, "linear combination too long");
-    int l = cts[0]->level, B = 1, np = 2;
-    for (int i = 0; i < n; i++) {
-        l = std::min(l, cts[i]->level);
-        B = std::max(B, cts[i]->B);
-        np = std::max(np, cts[i]->np);
-    }
-    for (int i = 0; i < n; i++)
-        if (cts[i]->B != B && cts[i]->B != 1) throw_err(AESFHE_EARG, "batch mismatch");
-    if (l < 1) throw_err(AESFHE_ELEVEL, "no level left for a linear combination");
-    const int nl = l + 1;
+    const OperandScan sc = lincomb_scan(cts, n);
+    const int l = sc.level, B = sc.B, np = sc.np, nl = l + 1;
     const double s = aesfhe_engine_mul_scale(e, l);
-    // gather the contributing inputs, each aligned to level l
-    std::vector<std::unique_ptr<Aligned>> al;
-    std::vector<const u64*> ptrs;
-    std::vector<long> bstr;
-    std::vector<int> npi;
+    // gather the contributing inputs, each truncated to level l
+    OperandTable tab;
     std::vector<u64> f;
     std::vector<double> ff;
-    std::vector<long> pss;
     for (int i = 0; i < n; i++) {
         // inputs above l are truncated to its limbs, their scale compensated in the constant
         const double si = s * (e->chain.scale[l] / e->chain.scale[cts[i]->level]);
         int64_t A = llround(re[i] * si), Bc = llround(im[i] * si);
-        if (cts[i]->is_zero || (A == 0 && Bc == 0)) continue;
-        const View v = trunc_view(cts[i], l);
-        ptrs.push_back(v.d);
-        bstr.push_back(v.B == 1 && B > 1 ? 0 : v.bs);
-        pss.push_back(v.ps);
-        npi.push_back(v.np);
+        if ((A == 0 && Bc == 0) || !tab.add(trunc_view(cts[i], l), B)) continue;
         std::vector<u64> fi;
         std::vector<double> ffi;
         const_factors(e, A, Bc, nl, fi, ffi);
         f.insert(f.end(), fi.begin(), fi.end());
         ff.insert(ff.end(), ffi.begin(), ffi.end());
     }
-    if (ptrs.empty()) {
-        *out = ct_zero_new(e, B, np, l - 1);
+    if (tab.empty()) {
+        *out = ct_zero_new(e, B, np, l - 1).release();
     } else {
-        const int m = (int)ptrs.size();
-        aesfhe_ct* acc = ct_new(e, B, np, l);
-        auto dp = upload_small(e, ptrs.data(), ptrs.size());
-        auto db = upload_small(e, bstr.data(), bstr.size());
-        auto dps = upload_small(e, pss.data(), pss.size());
-        auto dn = upload_small(e, npi.data(), npi.size());
+        const int m = (int)tab.size();
+        CtPtr acc = ct_new(e, B, np, l);
+        const DevOperands d = upload(e, {&tab}, OP_PTR | OP_BS | OP_PS | OP_NP)[0];
         auto df = upload_small(e, f.data(), f.size());
         auto dff = upload_small(e, ff.data(), ff.size());
         {
             ProfScope ps_(e, FAM_EW, 8.0 * e->N * nl * (double)B * np * (m + 1), "lincomb");
-            hipLaunchKernelGGL(k_lincomb, ew_grid(e, nl, B * np), dim3(256), 0, e->stream, (const u64* const*)dp, (const long*)db, (const int*)dn, m, (const long*)dps, (const u64*)df, (const double*)dff, out_of(acc), np, nl, e->q, e->qinv, e->logN);
+            hipLaunchKernelGGL(k_lincomb, ew_grid(e, nl, B * np), dim3(256), 0, e->stream, d.ptr, d.bs, d.np, m, d.ps, (const u64*)df, (const double*)dff, out_of(acc), np, nl, e->q, e->qinv, e->logN);
         }
         HIPC(hipGetLastError());
-        *out = rescale_view(e, view_of(acc));
-        aesfhe_ct_free(acc);
+        *out = rescale_view(e, view_of(acc)).release();
     }
     API_END
 }
@@ -3293,16 +3271,8 @@ extern "C" int aesfhe_lincomb_many(aesfhe_engine* e, const aesfhe_ct* const* cts
     }
     API_BEGIN
     if (n < 1) throw_err(AESFHE_EARG, "empty linear combination");
-    int l = cts[0]->level, B = 1, np = 2;
-    for (int i = 0; i < n; i++) {
-        l = std::min(l, cts[i]->level);
-        B = std::max(B, cts[i]->B);
-        np = std::max(np, cts[i]->np);
-    }
-    for (int i = 0; i < n; i++)
-        if (cts[i]->B != B && cts[i]->B != 1) throw_err(AESFHE_EARG, "batch mismatch");
-    if (l < 1) throw_err(AESFHE_ELEVEL, "no level left for a linear combination");
-    const int nl = l + 1;
+    const OperandScan sc = lincomb_scan(cts, n);
+    const int l = sc.level, B = sc.B, np = sc.np, nl = l + 1;
     const double s = aesfhe_engine_mul_scale(e, l);
     // rows whose constants all round to zero (or whose inputs are all zero) are zero outputs
     std::vector<int> live;
@@ -3315,24 +3285,14 @@ extern "C" int aesfhe_lincomb_many(aesfhe_engine* e, const aesfhe_ct* const* cts
             if (!cts[i]->is_zero && (A || Bc)) any = true, used[i] = 1;
         }
         if (any) live.push_back(r);
-        else outs[r] = nullptr;
     }
     std::vector<int> cols;
     for (int i = 0; i < n; i++)
         if (used[i]) cols.push_back(i);
-    std::vector<std::unique_ptr<Aligned>> al;
-    std::vector<const u64*> ptrs;
-    std::vector<long> bstr;
-    std::vector<int> npi;
-    std::vector<long> pss;
-    for (int i : cols) {  // truncated to level l (scale compensated in F below)
-        const View v = trunc_view(cts[i], l);
-        ptrs.push_back(v.d);
-        bstr.push_back(v.B == 1 && B > 1 ? 0 : v.bs);
-        pss.push_back(v.ps);
-        npi.push_back(v.np);
-    }
+    OperandTable tab;
+    for (int i : cols) tab.add(trunc_view(cts[i], l), B);  // truncated to level l (scale compensated in F below)
     const int nc = (int)cols.size(), ml = (int)live.size();
+    std::vector<CtPtr> res(m);
     if (ml > 0) {
         std::vector<u64> F((size_t)ml * nc * nl * 2);
         std::vector<double> FF(F.size());
@@ -3350,71 +3310,71 @@ extern "C" int aesfhe_lincomb_many(aesfhe_engine* e, const aesfhe_ct* const* cts
             }
         const long ps = (long)nl * e->N, obs = (long)np * ps, orow = (long)B * obs;
         Tmp acc(e, (size_t)ml * orow);
-        auto dp = upload_small(e, ptrs.data(), ptrs.size());
-        auto db = upload_small(e, bstr.data(), bstr.size());
-        auto dps = upload_small(e, pss.data(), pss.size());
-        auto dn = upload_small(e, npi.data(), npi.size());
+        const DevOperands d = upload(e, {&tab}, OP_PTR | OP_BS | OP_PS | OP_NP)[0];
         auto dF = upload_small(e, F.data(), F.size());
         auto dFF = upload_small(e, FF.data(), FF.size());
         {
             ProfScope ps_(e, FAM_EW, 8.0 * e->N * nl * (double)B * np * (nc + ml), "lincomb_many");
-            hipLaunchKernelGGL(k_lincomb_many, ew_grid(e, nl, B * np), dim3(256), 0, e->stream, (const u64* const*)dp, (const long*)db, (const int*)dn, nc, (const long*)dps, (const u64*)dF, (const double*)dFF, ml, acc.p, orow, obs, np, nl, e->q, e->qinv, e->logN);
+            hipLaunchKernelGGL(k_lincomb_many, ew_grid(e, nl, B * np), dim3(256), 0, e->stream, d.ptr, d.bs, d.np, nc, d.ps, (const u64*)dF, (const double*)dFF, ml, acc.p, orow, obs, np, nl, e->q, e->qinv, e->logN);
         }
         HIPC(hipGetLastError());
-        std::vector<aesfhe_ct*> res = rescale_groups(e, acc.p, ml, B, np, l);
-        for (int r = 0; r < ml; r++) outs[live[r]] = res[r];
+        std::vector<CtPtr> groups = rescale_groups(e, acc.p, ml, B, np, l);
+        for (int r = 0; r < ml; r++) res[live[r]] = std::move(groups[r]);
     }
     for (int r = 0; r < m; r++)
-        if (!outs[r]) outs[r] = ct_zero_new(e, B, np, l - 1);
+        if (!res[r]) res[r] = ct_zero_new(e, B, np, l - 1);
+    release_all(res, outs);
     API_END
+}
+
+// The factors of a dot product: a_0, b_0, a_1, b_1, ... must have 2 polynomials each.
+static std::vector<Operand> dot_factors(const aesfhe_ct* const* a, const aesfhe_ct* const* b, int n) {
+    std::vector<Operand> ab;
+    for (int i = 0; i < n; i++) ab.push_back(view_of(a[i])), ab.push_back(view_of(b[i]));
+    return ab;
+}
+// The products a_i b_i with both factors non-zero, each factor aligned to level l: the tables of
+// the a and the b factors (k_dot, k_dot_fma) and the level-downed copies they point into.
+struct Products {
+    std::vector<Aligned> al;
+    OperandTable a, b;
+};
+static void gather_products(aesfhe_engine* e, const aesfhe_ct* const* a, const aesfhe_ct* const* b, int n, int l, int B,
+                            Products& p) {
+    for (int i = 0; i < n; i++) {
+        if (a[i]->is_zero || b[i]->is_zero) continue;
+        for (const aesfhe_ct* c : {a[i], b[i]}) {
+            p.al.emplace_back();
+            align_to(e, c, l, p.al.back());
+        }
+        p.a.add(p.al[p.al.size() - 2].v, B);
+        p.b.add(p.al.back().v, B);
+    }
 }
 
 extern "C" int aesfhe_dot(aesfhe_engine* e, const aesfhe_ct* const* a, const aesfhe_ct* const* b, int32_t n, const aesfhe_key* rlk, aesfhe_ct** out) {
     API_BEGIN
     if (n < 1) throw_err(AESFHE_EARG, "empty dot product");
     if (!rlk || rlk->kind != 2) throw_err(AESFHE_EARG, "dot needs a relinearization key");
-    int l = a[0]->level, B = 1;
-    for (int i = 0; i < n; i++) {
-        if (a[i]->np != 2 || b[i]->np != 2) throw_err(AESFHE_EDEGREE, "dot inputs should have 2 polynomials");
-        l = std::min(l, std::min(a[i]->level, b[i]->level));
-        B = std::max(B, std::max(a[i]->B, b[i]->B));
-    }
-    for (int i = 0; i < n; i++)
-        if ((a[i]->B != B && a[i]->B != 1) || (b[i]->B != B && b[i]->B != 1)) throw_err(AESFHE_EARG, "batch mismatch");
+    const OperandScan sc = scan_operands(dot_factors(a, b, n), kNpTwo);
+    if (!sc.np_ok) throw_err(AESFHE_EDEGREE, "dot inputs should have 2 polynomials");
+    if (sc.mismatch) throw_err(AESFHE_EARG, "batch mismatch");
+    const int l = sc.level, B = sc.B, nl = l + 1;
     if (l < 1) throw_err(AESFHE_ELEVEL, "no level left for a dot product");
-    const int nl = l + 1;
-    std::vector<std::unique_ptr<Aligned>> al;
-    std::vector<const u64*> pa, pb;
-    std::vector<long> sa, sb;
-    for (int i = 0; i < n; i++) {
-        if (a[i]->is_zero || b[i]->is_zero) continue;
-        al.emplace_back(new Aligned());
-        align_to(e, a[i], l, *al.back());
-        const View va = al.back()->v;
-        al.emplace_back(new Aligned());
-        align_to(e, b[i], l, *al.back());
-        const View vb = al.back()->v;
-        pa.push_back(va.d);
-        pb.push_back(vb.d);
-        sa.push_back(va.B == 1 && B > 1 ? 0 : va.bs);
-        sb.push_back(vb.B == 1 && B > 1 ? 0 : vb.bs);
-    }
-    if (pa.empty()) {
-        *out = ct_zero_new(e, B, 2, l - 1);
+    Products pr;
+    gather_products(e, a, b, n, l, B, pr);
+    if (pr.a.empty()) {
+        *out = ct_zero_new(e, B, 2, l - 1).release();
     } else {
-        const int m = (int)pa.size();
-        aesfhe_ct* acc = ct_new(e, B, 3, l);
-        auto dpa = upload_small(e, pa.data(), pa.size());
-        auto dpb = upload_small(e, pb.data(), pb.size());
-        auto dsa = upload_small(e, sa.data(), sa.size());
-        auto dsb = upload_small(e, sb.data(), sb.size());
+        const int m = (int)pr.a.size();
+        CtPtr acc = ct_new(e, B, 3, l);
+        const auto d = upload(e, {&pr.a, &pr.b}, OP_PTR | OP_BS);
         {
             ProfScope ps_(e, FAM_EW, 8.0 * e->N * nl * (double)B * (4.0 * m + 3), "dot");
-            hipLaunchKernelGGL(k_dot, ew_grid(e, nl, B), dim3(256), 0, e->stream, (const u64* const*)dpa, (const long*)dsa, (const u64* const*)dpb, (const long*)dsb, m, (long)nl * e->N, out_of(acc), e->q, e->qinv, e->logN);
+            hipLaunchKernelGGL(k_dot, ew_grid(e, nl, B), dim3(256), 0, e->stream, d[0].ptr, d[0].bs, d[1].ptr, d[1].bs, m, (long)nl * e->N, out_of(acc), e->q, e->qinv, e->logN);
         }
         HIPC(hipGetLastError());
-        *out = relin_rescale(e, acc, rlk, 1);
-        aesfhe_ct_free(acc);
+        *out = relin_rescale(e, acc.get(), rlk, 1).release();
     }
     API_END
 }
@@ -3429,52 +3389,25 @@ extern "C" int aesfhe_dot_fma(aesfhe_engine* e, const aesfhe_ct* const* a, const
     if (n < 1) throw_err(AESFHE_EARG, "empty dot product");
     if (nc < 0) throw_err(AESFHE_EARG, "negative addend count");
     if (!rlk || rlk->kind != 2) throw_err(AESFHE_EARG, "dot needs a relinearization key");
-    int l = a[0]->level, B = 1;
-    for (int i = 0; i < n; i++) {
-        if (a[i]->np != 2 || b[i]->np != 2) throw_err(AESFHE_EDEGREE, "dot inputs should have 2 polynomials");
-        l = std::min(l, std::min(a[i]->level, b[i]->level));
-        B = std::max(B, std::max(a[i]->B, b[i]->B));
-    }
-    for (int j = 0; j < nc; j++) {
-        if (c[j]->np != 2) throw_err(AESFHE_EDEGREE, "dot_fma addends should have 2 polynomials");
-        B = std::max(B, c[j]->B);
-    }
+    const std::vector<Operand> ab = dot_factors(a, b, n), cv = views_of(c, nc);
+    const OperandScan sp = scan_operands(ab, kNpTwo), sa = scan_operands(cv, kNpTwo);
+    if (!sp.np_ok) throw_err(AESFHE_EDEGREE, "dot inputs should have 2 polynomials");
+    if (!sa.np_ok) throw_err(AESFHE_EDEGREE, "dot_fma addends should have 2 polynomials");
+    const int l = sp.level, B = std::max(sp.B, sa.B), nl = l + 1;
     for (int j = 0; j < nc; j++)
         if (c[j]->level < l) throw_err(AESFHE_ELEVEL, "dot_fma addend level %d below the product level %d", c[j]->level, l);
-    for (int i = 0; i < n; i++)
-        if ((a[i]->B != B && a[i]->B != 1) || (b[i]->B != B && b[i]->B != 1)) throw_err(AESFHE_EARG, "batch mismatch");
-    for (int j = 0; j < nc; j++)
-        if (c[j]->B != B && c[j]->B != 1) throw_err(AESFHE_EARG, "batch mismatch");
+    if (batch_mismatch(ab, B) || batch_mismatch(cv, B)) throw_err(AESFHE_EARG, "batch mismatch");
     if (l < 1) throw_err(AESFHE_ELEVEL, "no level left for a dot product");
-    const int nl = l + 1;
-    std::vector<std::unique_ptr<Aligned>> al;
-    std::vector<const u64*> pa, pb;
-    std::vector<long> sa, sb;
-    for (int i = 0; i < n; i++) {
-        if (a[i]->is_zero || b[i]->is_zero) continue;
-        al.emplace_back(new Aligned());
-        align_to(e, a[i], l, *al.back());
-        const View va = al.back()->v;
-        al.emplace_back(new Aligned());
-        align_to(e, b[i], l, *al.back());
-        const View vb = al.back()->v;
-        pa.push_back(va.d);
-        pb.push_back(vb.d);
-        sa.push_back(va.B == 1 && B > 1 ? 0 : va.bs);
-        sb.push_back(vb.B == 1 && B > 1 ? 0 : vb.bs);
-    }
+    check_key_digits(e, rlk, l);
+    Products pr;
+    gather_products(e, a, b, n, l, B, pr);
     // addends: truncated views, C_j per limb
     const double* D = e->chain.scale.data();
-    std::vector<const u64*> cp;
-    std::vector<long> cbs, cps;
+    OperandTable tc;
     std::vector<u64> cf;
     for (int j = 0; j < nc; j++) {
         const int64_t Cc = llround(gamma[j] * (D[l] * (D[l] / D[c[j]->level])));
-        if (c[j]->is_zero || Cc == 0) continue;
-        const View v = trunc_view(c[j], l);
-        cp.push_back(v.d);
-        cbs.push_back(v.B == 1 && B > 1 ? 0 : v.bs);
-        cps.push_back(v.ps);
+        if (Cc == 0 || !tc.add(trunc_view(c[j], l), B)) continue;
         for (int i = 0; i < nl; i++) cf.push_back(h_smod(Cc, e->chain.q[i]));
     }
     const int64_t Rb = llround(beta * D[l]), R = llround(D[l]);
@@ -3483,30 +3416,19 @@ extern "C" int aesfhe_dot_fma(aesfhe_engine* e, const aesfhe_ct* const* a, const
         const u64 q = e->chain.q[i];
         km[i] = h_mulmod(h_smod(Rb, q), h_smod(R, q), q);
     }
-    aesfhe_ct* acc = ct_new(e, B, 3, l);
-    try {
-        const int m = (int)pa.size(), mc = (int)cp.size();
-        const u64* const* dpa = m ? (const u64* const*)upload_small(e, pa.data(), pa.size()) : nullptr;
-        const u64* const* dpb = m ? (const u64* const*)upload_small(e, pb.data(), pb.size()) : nullptr;
-        const long* dsa = m ? upload_small(e, sa.data(), sa.size()) : nullptr;
-        const long* dsb = m ? upload_small(e, sb.data(), sb.size()) : nullptr;
-        const u64* const* dcp = mc ? (const u64* const*)upload_small(e, cp.data(), cp.size()) : nullptr;
-        const long* dcb = mc ? upload_small(e, cbs.data(), cbs.size()) : nullptr;
-        const long* dcs = mc ? upload_small(e, cps.data(), cps.size()) : nullptr;
-        const u64* dcf = mc ? upload_small(e, cf.data(), cf.size()) : nullptr;
-        const u64* dkm = upload_small(e, km.data(), km.size());
-        {
-            ProfScope ps_(e, FAM_EW, 8.0 * e->N * nl * (double)B * (4.0 * m + 2.0 * mc + 3), "dot");
-            hipLaunchKernelGGL(k_dot_fma, ew_grid(e, nl, B), dim3(256), 0, e->stream, dpa, dsa, dpb, dsb, m, (long)nl * e->N,
-                               dcp, dcb, dcs, mc, dcf, dkm, nl, out_of(acc), e->q, e->qinv, e->logN);
-        }
-        HIPC(hipGetLastError());
-        *out = relin_rescale(e, acc, rlk, 1);
-    } catch (...) {
-        aesfhe_ct_free(acc);
-        throw;
+    CtPtr acc = ct_new(e, B, 3, l);
+    const int m = (int)pr.a.size(), mc = (int)tc.size();
+    const auto dp = upload(e, {&pr.a, &pr.b}, OP_PTR | OP_BS);  // nothing uploaded (nullptr) without products / addends
+    const DevOperands dc = upload(e, {&tc}, OP_PTR | OP_BS | OP_PS)[0];
+    const u64* dcf = mc ? upload_small(e, cf.data(), cf.size()) : nullptr;
+    const u64* dkm = upload_small(e, km.data(), km.size());
+    {
+        ProfScope ps_(e, FAM_EW, 8.0 * e->N * nl * (double)B * (4.0 * m + 2.0 * mc + 3), "dot");
+        hipLaunchKernelGGL(k_dot_fma, ew_grid(e, nl, B), dim3(256), 0, e->stream, dp[0].ptr, dp[0].bs, dp[1].ptr, dp[1].bs, m, (long)nl * e->N,
+                           dc.ptr, dc.bs, dc.ps, mc, dcf, dkm, nl, out_of(acc), e->q, e->qinv, e->logN);
     }
-    aesfhe_ct_free(acc);
+    HIPC(hipGetLastError());
+    *out = relin_rescale(e, acc.get(), rlk, 1).release();
     API_END
 }
 
@@ -3553,26 +3475,58 @@ static TwD* poly2_table(aesfhe_engine* e, int l, int nx, int ny, int m, const st
     return d;
 }
 
-extern "C" int aesfhe_poly2(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_t nx, const aesfhe_ct* const* yb, int32_t ny, const double* re, const double* im, int32_t m, const aesfhe_key* rlk, aesfhe_ct** outs) {
-    API_BEGIN
+// What aesfhe_poly2 and aesfhe_poly2_int share.
+// The argument checks; returns the scan of the basis ciphertexts (lowest level l >= 2, batch B).
+static OperandScan poly2_check(const aesfhe_ct* const* xb, int nx, const aesfhe_ct* const* yb, int ny, int m,
+                               const aesfhe_key* rlk, int den = 1) {
     if (nx < 1 || ny < 1 || nx > kPoly2Max || ny > kPoly2Max || m < 1)
         throw_err(AESFHE_EARG, "poly2 needs 1 <= nx, ny <= %d and m >= 1", kPoly2Max);
     if (nx + ny < 3) throw_err(AESFHE_EARG, "poly2 needs at least one basis ciphertext");
+    if (den < 1) throw_err(AESFHE_EARG, "poly2_int needs den >= 1");
     if (!rlk || rlk->kind != 2) throw_err(AESFHE_EARG, "poly2 needs a relinearization key");
-    std::vector<const aesfhe_ct*> all;
-    for (int i = 0; i < nx - 1; i++) all.push_back(xb[i]);
-    for (int j = 0; j < ny - 1; j++) all.push_back(yb[j]);
-    int l = all[0]->level, B = 1;
-    for (auto* c : all) {
-        if (c->np != 2) throw_err(AESFHE_EDEGREE, "poly2 inputs should have 2 polynomials");
-        if (c->is_zero) throw_err(AESFHE_EARG, "poly2 basis ciphertext is zero");
-        l = std::min(l, c->level);
-        B = std::max(B, c->B);
+    std::vector<Operand> all = views_of(xb, nx - 1);
+    for (int j = 0; j < ny - 1; j++) all.push_back(view_of(yb[j]));
+    const OperandScan sc = scan_operands(all, kNpTwo);
+    if (!sc.np_ok) throw_err(AESFHE_EDEGREE, "poly2 inputs should have 2 polynomials");
+    if (sc.any_zero) throw_err(AESFHE_EARG, "poly2 basis ciphertext is zero");
+    if (sc.mismatch) throw_err(AESFHE_EARG, "batch mismatch");
+    if (sc.level < 2) throw_err(AESFHE_ELEVEL, "no level left for a bivariate polynomial");
+    return sc;
+}
+// The table of one basis b = b^1..b^{n-1} in the kernel's order (power i is b[perm[i] - 1];
+// perm == nullptr: as given), truncated to level l by reading limbs 0..l in place; an empty basis
+// gets the null placeholder.
+static OperandTable poly2_basis(const aesfhe_ct* const* b, int n, const int* perm, int B) {
+    OperandTable t;
+    for (int i = 1; i < n; i++) {
+        const View v = view_of(b[(perm ? perm[i] : i) - 1]);
+        if (v.B > 1 && !v.compact()) throw_err(AESFHE_EARG, "poly2: non-compact basis view");
+        t.add(v, B);
     }
-    for (auto* c : all)
-        if (c->B != B && c->B != 1) throw_err(AESFHE_EARG, "batch mismatch");
-    if (l < 2) throw_err(AESFHE_ELEVEL, "no level left for a bivariate polynomial");
-    const int nl = l + 1, N = e->N;
+    if (t.empty()) t.add_null();
+    return t;
+}
+// The tail: d3, the tensor sums of the live outputs as one batch (live.size() x B; empty without
+// live outputs), is relinearised and rescaled twice in one pass and split per output (no
+// copies); the dead outputs are zero ciphertexts.
+static void poly2_finish(aesfhe_engine* e, CtPtr d3, const aesfhe_key* rlk, const std::vector<int>& live, int m, int B,
+                         int l, aesfhe_ct** outs) {
+    std::vector<CtPtr> res(m);
+    if (!live.empty()) {
+        CtPtr r2 = relin_rescale(e, d3.get(), rlk, 2);
+        d3.reset();
+        std::vector<CtPtr> parts = ct_split_batch(e, std::move(r2), (int)live.size());
+        for (size_t t = 0; t < live.size(); t++) res[live[t]] = std::move(parts[t]);
+    }
+    for (int t = 0; t < m; t++)
+        if (!res[t]) res[t] = ct_zero_new(e, B, 2, l - 2);
+    release_all(res, outs);
+}
+
+extern "C" int aesfhe_poly2(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_t nx, const aesfhe_ct* const* yb, int32_t ny, const double* re, const double* im, int32_t m, const aesfhe_key* rlk, aesfhe_ct** outs) {
+    API_BEGIN
+    const OperandScan sc = poly2_check(xb, nx, yb, ny, m, rlk);
+    const int l = sc.level, B = sc.B, nl = l + 1, N = e->N;
     const double* D = e->chain.scale.data();
     const double S1 = D[l - 2] / D[l] * ((double)e->chain.q[l] / D[l]) * (double)e->chain.q[l - 1];
     const int64_t R = llround(D[l]);
@@ -3589,10 +3543,7 @@ extern "C" int aesfhe_poly2(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_
         bool any = false;
         for (size_t c = 0; c < per; c++)
             if (coef(re, t, c) || coef(im, t, c)) any = true;
-        if (!any) {
-            outs[t] = nullptr;
-            continue;
-        }
+        if (!any) continue;
         live.push_back(t);
         for (size_t c = 0; c < per; c++) {
             A.push_back(coef(re, t, c));
@@ -3600,41 +3551,22 @@ extern "C" int aesfhe_poly2(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_
         }
     }
     const int ml = (int)live.size();
+    CtPtr d3;
     if (ml > 0) {
-        std::vector<const u64*> px, py;
-        std::vector<long> sx, sy, qx, qy;
-        for (size_t a = 0; a < all.size(); a++) {
-            const View v = view_of(all[a]);  // truncation: limbs 0..l read in place
-            if (v.B > 1 && v.bs != (long)v.np * v.ps) throw_err(AESFHE_EARG, "poly2: non-compact basis view");
-            const long bs = v.B == 1 && B > 1 ? 0 : v.bs;
-            if ((int)a < nx - 1) px.push_back(v.d), sx.push_back(bs), qx.push_back(v.ps);
-            else py.push_back(v.d), sy.push_back(bs), qy.push_back(v.ps);
-        }
-        if (px.empty()) px.push_back(nullptr), sx.push_back(0), qx.push_back(0);
-        if (py.empty()) py.push_back(nullptr), sy.push_back(0), qy.push_back(0);
+        const OperandTable tx = poly2_basis(xb, nx, nullptr, B), ty = poly2_basis(yb, ny, nullptr, B);
         const TwD* tab = poly2_table(e, l, nx, ny, ml, A, Bc, R);
-        auto dpx = upload_small(e, px.data(), px.size());
-        auto dpy = upload_small(e, py.data(), py.size());
-        auto dsx = upload_small(e, sx.data(), sx.size());
-        auto dsy = upload_small(e, sy.data(), sy.size());
-        auto dqx = upload_small(e, qx.data(), qx.size());
-        auto dqy = upload_small(e, qy.data(), qy.size());
+        const auto d = upload(e, {&tx, &ty}, OP_PTR | OP_BS | OP_PS);
         const int Bt = ml * B;
         const long obs = 3L * nl * N;
-        aesfhe_ct* d3 = ct_new(e, Bt, 3, l);
+        d3 = ct_new(e, Bt, 3, l);
         {
             ProfScope ps_(e, FAM_EW, 8.0 * N * nl * (double)B * (2.0 * (nx + ny - 2) + 3.0 * ml), "poly2");
             for (int t0 = 0; t0 < ml; t0 += kPoly2Out)
-                hipLaunchKernelGGL(k_poly2, ew_grid(e, nl, B), dim3(256), 0, e->stream, (const u64* const*)dpx, (const long*)dsx, (const long*)dqx, nx, (const u64* const*)dpy, (const long*)dsy, (const long*)dqy, ny, tab, ml, t0, std::min(kPoly2Out, ml - t0), d3->d, (long)B * obs, obs, e->q, e->qinv, e->logN);
+                hipLaunchKernelGGL(k_poly2, ew_grid(e, nl, B), dim3(256), 0, e->stream, d[0].ptr, d[0].bs, d[0].ps, nx, d[1].ptr, d[1].bs, d[1].ps, ny, tab, ml, t0, std::min(kPoly2Out, ml - t0), d3->d, (long)B * obs, obs, e->q, e->qinv, e->logN);
         }
         HIPC(hipGetLastError());
-        aesfhe_ct* r2 = relin_rescale(e, d3, rlk, 2);
-        aesfhe_ct_free(d3);
-        std::vector<aesfhe_ct*> parts = ct_split_batch(e, r2, ml);  // no copies
-        for (int t = 0; t < ml; t++) outs[live[t]] = parts[t];
     }
-    for (int t = 0; t < m; t++)
-        if (!outs[t]) outs[t] = ct_zero_new(e, B, 2, l - 2);
+    poly2_finish(e, std::move(d3), rlk, live, m, B, l, outs);
     API_END
 }
 
@@ -3664,25 +3596,8 @@ extern "C" int aesfhe_poly2_int_rot(aesfhe_engine* e, const aesfhe_ct* const* xb
 static void poly2_int_impl(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_t nx, const aesfhe_ct* const* yb,
                            int32_t ny, const int32_t* w, int32_t den, int32_t m, const aesfhe_key* rlk,
                            aesfhe_ct** outs, int slab_rot) {
-    if (nx < 1 || ny < 1 || nx > kPoly2Max || ny > kPoly2Max || m < 1)
-        throw_err(AESFHE_EARG, "poly2 needs 1 <= nx, ny <= %d and m >= 1", kPoly2Max);
-    if (nx + ny < 3) throw_err(AESFHE_EARG, "poly2 needs at least one basis ciphertext");
-    if (den < 1) throw_err(AESFHE_EARG, "poly2_int needs den >= 1");
-    if (!rlk || rlk->kind != 2) throw_err(AESFHE_EARG, "poly2 needs a relinearization key");
-    int l = INT32_MAX, B = 1;
-    auto check = [&](const aesfhe_ct* c) {
-        if (c->np != 2) throw_err(AESFHE_EDEGREE, "poly2 inputs should have 2 polynomials");
-        if (c->is_zero) throw_err(AESFHE_EARG, "poly2 basis ciphertext is zero");
-        l = std::min(l, c->level);
-        B = std::max(B, c->B);
-    };
-    for (int i = 0; i < nx - 1; i++) check(xb[i]);
-    for (int j = 0; j < ny - 1; j++) check(yb[j]);
-    for (int i = 0; i < nx - 1; i++)
-        if (xb[i]->B != B && xb[i]->B != 1) throw_err(AESFHE_EARG, "batch mismatch");
-    for (int j = 0; j < ny - 1; j++)
-        if (yb[j]->B != B && yb[j]->B != 1) throw_err(AESFHE_EARG, "batch mismatch");
-    if (l < 2) throw_err(AESFHE_ELEVEL, "no level left for a bivariate polynomial");
+    const OperandScan sc = poly2_check(xb, nx, yb, ny, m, rlk, den);
+    const int l = sc.level, B = sc.B;
     if (slab_rot && B % 4) throw_err(AESFHE_EARG, "slab rotation needs a batch of whole slabs (4 s), got %d", B);
     // wfac bounds an inner sum a = w_0 c0 + sum_j w_j y'_j (c0 < q, |y'| <= q/2 + 1) by wfac * q:
     // a limb takes the exact-FMA kernel (no folds) when wfac * q < 2^52, else the folding one
@@ -3730,15 +3645,13 @@ static void poly2_int_impl(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_t
     for (int t = 0; t < m; t++) {
         bool any = false;
         for (size_t c = 0; c < (size_t)nx * ny; c++) any |= w[(size_t)t * nx * ny + c] != 0;
-        if (!any) {
-            outs[t] = nullptr;
-            continue;
-        }
+        if (!any) continue;
         live.push_back(t);
         for (int i = 0; i < nx; i++)
             for (int j = 0; j < ny; j++) Wt.push_back((double)w[((size_t)t * nx + permx[i]) * ny + perm[j]]);
     }
     const int ml = (int)live.size();
+    CtPtr d3;
     if (ml > 0) {
         // y' factors Rt[c][cy] = H(c, cy), C0[c] = H(c, 0)
         std::vector<TwD> Rt((size_t)nl * cxn * cyn);
@@ -3764,26 +3677,8 @@ static void poly2_int_impl(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_t
                 }
             }
         }
-        std::vector<const u64*> px, py;
-        std::vector<long> sx, sy, qx, qy;
-        for (int i = 1; i < nx; i++) {
-            const View v = view_of(xb[permx[i] - 1]);
-            if (v.B > 1 && v.bs != (long)v.np * v.ps) throw_err(AESFHE_EARG, "poly2: non-compact basis view");
-            px.push_back(v.d), sx.push_back(v.B == 1 && B > 1 ? 0 : v.bs), qx.push_back(v.ps);
-        }
-        for (int j = 1; j < ny; j++) {
-            const View v = view_of(yb[perm[j] - 1]);
-            if (v.B > 1 && v.bs != (long)v.np * v.ps) throw_err(AESFHE_EARG, "poly2: non-compact basis view");
-            py.push_back(v.d), sy.push_back(v.B == 1 && B > 1 ? 0 : v.bs), qy.push_back(v.ps);
-        }
-        if (px.empty()) px.push_back(nullptr), sx.push_back(0), qx.push_back(0);
-        if (py.empty()) py.push_back(nullptr), sy.push_back(0), qy.push_back(0);
-        auto dpx = upload_small(e, px.data(), px.size());
-        auto dpy = upload_small(e, py.data(), py.size());
-        auto dsx = upload_small(e, sx.data(), sx.size());
-        auto dsy = upload_small(e, sy.data(), sy.size());
-        auto dqx = upload_small(e, qx.data(), qx.size());
-        auto dqy = upload_small(e, qy.data(), qy.size());
+        const OperandTable tx = poly2_basis(xb, nx, permx.data(), B), ty = poly2_basis(yb, ny, perm.data(), B);
+        const auto d = upload(e, {&tx, &ty}, OP_PTR | OP_BS | OP_PS);
         std::vector<int> xstart(cxn + 1, nx);
         for (int i = nx - 1; i >= 0; i--) xstart[cxs[i]] = i;
         auto dcx = upload_small(e, xstart.data(), xstart.size());
@@ -3792,7 +3687,7 @@ static void poly2_int_impl(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_t
         auto dR = upload_small(e, Rt.data(), Rt.size());
         auto dC0 = upload_small(e, C0.data(), C0.size());
         const long obs = 3L * nl * N;
-        aesfhe_ct* d3 = ct_new(e, ml * B, 3, l);
+        d3 = ct_new(e, ml * B, 3, l);
         // a < 2^52 and the unfolded tensor sums (a + 2 (nx - 1) products of <= 1.5 q) < 2^53
         auto is_big = [&](int li) {
             const double q = (double)e->chain.q[li];
@@ -3830,13 +3725,13 @@ static void poly2_int_impl(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_t
                     for (int li = la; li < lb; li++) split &= (double)e->chain.q[li] < 0x1p51;
                     if (sbox && split) {
                         hipLaunchKernelGGL(k_poly2_int_split<mo>, dim3(2 * N / 256, lb - la, B), dim3(256), 0, e->stream,
-                                           (const u64* const*)dpx, (const long*)dsx, (const long*)dqx, nx, (const u64* const*)dpy, (const long*)dsy, (const long*)dqy,
+                                           d[0].ptr, d[0].bs, d[0].ps, nx, d[1].ptr, d[1].bs, d[1].ps,
                                            (const int*)dcx, (const int*)dcy, cxn, cyn, (const double*)dW, (const TwD*)dR, (const double*)dC0, t0,
                                            d3->d, (long)B * obs, obs, e->q, e->qinv, la, nl, e->logN, slab_rot);
                         ps_.disp++;
                     } else if (sbox) {
                         hipLaunchKernelGGL((big ? k_poly2_int_s<mo, false, true> : lz ? k_poly2_int_s<mo, true> : k_poly2_int_s<mo, false>), dim3(2 * N / 256, lb - la, B), dim3(256), 0, e->stream,
-                                           (const u64* const*)dpx, (const long*)dsx, (const long*)dqx, nx, (const u64* const*)dpy, (const long*)dsy, (const long*)dqy,
+                                           d[0].ptr, d[0].bs, d[0].ps, nx, d[1].ptr, d[1].bs, d[1].ps,
                                            (const int*)dcx, (const int*)dcy, cxn, cyn, (const double*)dW, (const TwD*)dR, (const double*)dC0, t0,
                                            d3->d, (long)B * obs, obs, e->q, e->qinv, la, nl, e->logN, slab_rot);
                         ps_.disp++;
@@ -3844,7 +3739,7 @@ static void poly2_int_impl(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_t
                         auto kern = big ? (ny == kPoly2Max ? k_poly2_int<true, kPoly2Max, mo> : k_poly2_int<true, 0, mo>)
                                         : (ny == kPoly2Max ? k_poly2_int<false, kPoly2Max, mo> : k_poly2_int<false, 0, mo>);
                         for (int tb = t0; tb < (sbox ? t0 + 2 * mo : t0 + mo) && tb < ml; tb += mo) {
-                            hipLaunchKernelGGL(kern, grid, dim3(256), 0, e->stream, (const u64* const*)dpx, (const long*)dsx, (const long*)dqx, nx, (const u64* const*)dpy, (const long*)dsy, (const long*)dqy, ny,
+                            hipLaunchKernelGGL(kern, grid, dim3(256), 0, e->stream, d[0].ptr, d[0].bs, d[0].ps, nx, d[1].ptr, d[1].bs, d[1].ps, ny,
                                                (const int*)dcx, (const int*)dcy, cxn, cyn, (const double*)dW, (const TwD*)dR, (const double*)dC0, ml, tb, std::min(mo, ml - tb), d3->d, (long)B * obs, obs, e->q, e->qinv, la, nl, e->logN, slab_rot);
                             ps_.disp++;
                         }
@@ -3855,13 +3750,8 @@ static void poly2_int_impl(aesfhe_engine* e, const aesfhe_ct* const* xb, int32_t
             }
         }
         HIPC(hipGetLastError());
-        aesfhe_ct* r2 = relin_rescale(e, d3, rlk, 2);
-        aesfhe_ct_free(d3);
-        std::vector<aesfhe_ct*> parts = ct_split_batch(e, r2, ml);  // no copies
-        for (int t = 0; t < ml; t++) outs[live[t]] = parts[t];
     }
-    for (int t = 0; t < m; t++)
-        if (!outs[t]) outs[t] = ct_zero_new(e, B, 2, l - 2);
+    poly2_finish(e, std::move(d3), rlk, live, m, B, l, outs);
 }
 
 // -----------------------------------------------------------------------------------------------

@@ -22,22 +22,20 @@ extern "C" int aesfhe_ptb_create_device(aesfhe_engine* e, const int64_t* co, int
     if (level < 0 || level > e->L) throw_err(AESFHE_EARG, "bad plaintext level");
     if (B < 1 || B > kMaxGridZ) throw_err(AESFHE_EARG, "plaintext batch %d not in 1..%d", B, kMaxGridZ);
     const int N = e->N, nl = level + 1;
-    auto* p = new aesfhe_ptb{e, B, level, nullptr, (size_t)B * nl * N * 8};
+    struct PtbFree {
+        void operator()(aesfhe_ptb* p) const { aesfhe_ptb_free(p); }
+    };
+    std::unique_ptr<aesfhe_ptb, PtbFree> p(new aesfhe_ptb{e, B, level, nullptr, (size_t)B * nl * N * 8});
     e->refs++;
-    try {
-        p->d = (u64*)pool_get(e, p->bytes);
-        {
-            ProfScope ps(e, FAM_EW, 8.0 * N * (double)B * (1 + nl), "ptb_create");
-            hipLaunchKernelGGL(k_coeffs_res_batch, dim3(N / 512, nl, B), dim3(256), 0, e->stream, (const i64*)co, p->d, nl, e->q, e->logN);
-        }
-        HIPC(hipGetLastError());
-        Span s = span_s(p->d, (long)nl * N, nl, nl, 0, e->Lp1);
-        ntt(e, s, s, B * nl, false);
-    } catch (...) {
-        aesfhe_ptb_free(p);
-        throw;
+    p->d = (u64*)pool_get(e, p->bytes);
+    {
+        ProfScope ps(e, FAM_EW, 8.0 * N * (double)B * (1 + nl), "ptb_create");
+        hipLaunchKernelGGL(k_coeffs_res_batch, dim3(N / 512, nl, B), dim3(256), 0, e->stream, (const i64*)co, p->d, nl, e->q, e->logN);
     }
-    *out = p;
+    HIPC(hipGetLastError());
+    Span s = span_s(p->d, (long)nl * N, nl, nl, 0, e->Lp1);
+    ntt(e, s, s, B * nl, false);
+    *out = p.release();
     API_END
 }
 
@@ -65,26 +63,18 @@ extern "C" int aesfhe_mul_ptb(aesfhe_engine* e, const aesfhe_ct* c, const aesfhe
     if (c->level < 1) throw_err(AESFHE_ELEVEL, "no level left for a plaintext multiplication");
     if (pt->level < c->level) throw_err(AESFHE_EARG, "plaintext level %d below ciphertext level %d", pt->level, c->level);
     if (c->is_zero) {
-        *out = ct_zero_new(e, Bp, c->np, c->level - 1);
+        *out = ct_zero_new(e, Bp, c->np, c->level - 1).release();
     } else {
         const int N = e->N, nl = c->level + 1;
         const View v = view_of(c);
-        aesfhe_ct* t = ct_new(e, Bp, c->np, c->level);
+        CtPtr t = ct_new(e, Bp, c->np, c->level);
         {
             ProfScope ps(e, FAM_EW, 8.0 * N * nl * (double)Bp * (1 + 2 * c->np), "mul_ptb");
             hipLaunchKernelGGL(k_mul_ptb, dim3(N / 512, nl, Bp), dim3(256), 0, e->stream, v.d, v.bs, v.ps, Bc, c->np,
                                (const u64*)pt->d, (long)(pt->level + 1) * N, t->d, e->q, e->qinv, e->logN);
         }
-        aesfhe_ct* r = nullptr;
-        try {
-            HIPC(hipGetLastError());
-            r = rescale_view(e, view_of(t));
-        } catch (...) {
-            aesfhe_ct_free(t);
-            throw;
-        }
-        aesfhe_ct_free(t);
-        *out = r;
+        HIPC(hipGetLastError());
+        *out = rescale_view(e, view_of(t)).release();
     }
     API_END
 }

@@ -63,3 +63,15 @@ def test_bsgs_plan_asan(tmp_path):
                     "-o", str(exe), str(ROOT / "tests" / "native" / "bsgs_plan_asan.cpp")], check=True)
     r = subprocess.run([str(exe)], env=ENV, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "bsgs_plan_asan ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+
+
+def test_operands_asan(tmp_path):
+    """The operand scan and table of the many-operand entry points (aes-fhe_amd/csrc/operands.h:
+    lowest level / largest batch / polynomial count, the batch-mismatch rule, broadcast strides,
+    zero operands skipped, input order kept) under ASan + UBSan against a direct model
+    (tests/native/operands_asan.cpp)."""
+    exe = tmp_path / "operands_asan"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+                    "-o", str(exe), str(ROOT / "tests" / "native" / "operands_asan.cpp")], check=True)
+    r = subprocess.run([str(exe)], env=ENV, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "operands_asan ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
