@@ -36,6 +36,7 @@ from aes_xor_fhe.fhe import Engine, widest_digits
 
 from _ks_helpers import (N16, _check_construction, _check_path, _compare, _drop, _expect_out,  # noqa: E402
                          _extreme_ct, _keys, _ntt, _pair, _pool, _profiled, _sweep, ks_plan)
+from _int_refs import tensor_ref as _tensor_ref  # noqa: E402  (the exact references live in one file)
 
 BIG = 1 << 42  # kernels.h kBigPrime
 
@@ -236,18 +237,6 @@ def _const_pool(primes, l, B, npoly, value, n=N12):
     out = np.empty((B, npoly, l + 1, n), dtype=np.uint64)
     for i in range(l + 1):
         out[:, :, i] = value(primes[i])
-    return out
-
-
-def _tensor_ref(a, b, primes):
-    """(a0 b0, a0 b1 + a1 b0, a1 b1) mod q per limb in Python integers: (B, 3, l + 1, n)."""
-    ao, bo = a.astype(object), b.astype(object)
-    out = np.empty((a.shape[0], 3) + a.shape[2:], dtype=np.uint64)
-    for i in range(a.shape[2]):
-        q = primes[i]
-        out[:, 0, i] = (ao[:, 0, i] * bo[:, 0, i]) % q
-        out[:, 1, i] = (ao[:, 0, i] * bo[:, 1, i] + ao[:, 1, i] * bo[:, 0, i]) % q
-        out[:, 2, i] = (ao[:, 1, i] * bo[:, 1, i]) % q
     return out
 
 
