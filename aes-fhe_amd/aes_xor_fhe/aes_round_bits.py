@@ -559,6 +559,114 @@ class AESSlicedRound(AESRowRound):
         rows = [np.repeat(rk[[r + 4 * c for c in range(4)]], self.sc).reshape(4, self.sc) for r in range(4)]
         return self.encrypt_bytes_rows(rows, level=level)
 
+    # ---- the key bundle: 11 round keys in one ciphertext -----------------
+    # Every ciphertext of encrypt_round_key holds a constant polynomial (the same +-1 in every slot:
+    # only coefficient 0 is non-zero), so all 11 x 4 x 8 x 4 = 1408 of them fit in the coefficients
+    # of one ciphertext, which the server unpacks with Engine.expand.
+    BUNDLE_COEFFS = 2048  # 128 (row, bit, column) positions x 16 key slots (11 used)
+    BUNDLE_STAGE2 = 7  # expansion steps 4..10, run per key
+    BUNDLE_GAIN_BITS = 10  # the bundle's bits sit 2^10 / 2^7 above Delta: the fresh noise counts 2^-10
+
+    @staticmethod
+    def bundle_index(k: int, r: int, j: int, c: int) -> int:
+        """Coefficient of round key k, row r, bit j, column c: the key index in the low 4 bits, so
+        that the first four expansion steps separate the keys and each key's 128 elements are
+        expanded at that key's own level."""
+        return ((r * 8 + j) * 4 + c) * 16 + k
+
+    def _bundle_ring(self) -> int:
+        n = 2 * self.sc
+        if n < self.BUNDLE_COEFFS:
+            raise ValueError(f"a key bundle needs {self.BUNDLE_COEFFS} coefficients: N = {n} is too small "
+                             f"(N >= 2^11)")
+        return n
+
+    def bundle_amplitude(self, level: int) -> int:
+        """|coefficient| of a key bit in a bundle encrypted at `level`."""
+        return int(round(self.e.scales[level] * 2.0 ** (self.BUNDLE_GAIN_BITS - self.BUNDLE_STAGE2)))
+
+    def pack_round_keys(self, rks, level: int | None = None) -> np.ndarray:
+        """11 round keys (11, 16) bytes -> the (1, N) int64 coefficients of a bundle encrypted at
+        `level` (one above the highest key level): coefficient bundle_index(k, r, j, c) =
+        (-1)^bit * bundle_amplitude(level), bit = bit j of byte r + 4c of key k."""
+        n = self._bundle_ring()
+        level = self.e.max_level if level is None else int(level)
+        rk = np.asarray(rks, dtype=np.int64)
+        if rk.shape != (11, 16):
+            raise ValueError(f"expected 11 round keys of 16 bytes, got {rk.shape}")
+        amp = self.bundle_amplitude(level)
+        co = np.zeros((1, n), dtype=np.int64)
+        k = np.arange(11)
+        for r in range(4):
+            for j in range(8):
+                for c in range(4):
+                    co[0, self.bundle_index(k, r, j, c)] = amp * (1 - 2 * ((rk[:, r + 4 * c] >> j) & 1))
+        return co
+
+    def encrypt_key_bundle(self, rks, level: int | None = None) -> Ciphertext:
+        """The client's whole key upload: one ciphertext (batch 1) at `level`, which must be one
+        above the highest level a key is wanted at (expand_round_keys)."""
+        level = self.e.max_level if level is None else int(level)
+        return self.e.encrypt_coefficients(self.pack_round_keys(rks, level), self.pk, level)
+
+    def create_key_expansion_keys(self) -> list:
+        """The 11 galois keys (g = N / 2^j + 1, j = 0..10) expand_round_keys switches with."""
+        self._bundle_ring()
+        return self.e.create_expansion_keys(self.sk, 0, 11)
+
+    def _times(self, ct: Ciphertext, m: int) -> Ciphertext:
+        """ct times the positive integer m, exactly and without a level: double and add."""
+        acc = ct
+        for bit in bin(m)[3:]:
+            acc = self.e.add(acc, acc)
+            if bit == "1":
+                acc = self.e.add(acc, ct)
+        return acc
+
+    def expand_key_subtree(self, el: Ciphertext, xkeys, level: int, bundle_level: int) -> Ciphertext:
+        """One key's element of the first stage (batch 1, its bits at bundle_amplitude) -> the 128
+        elements (r * 8 + j) * 4 + c of that key at `level`, +-Delta_level each.
+
+        The second stage runs one level up, at the squared scale: the element is brought to
+        level + 1, multiplied by the integer C ~ q_{level+1} / 2^10 that takes its bits to
+        Delta_level q_{level+1} / 2^7, expanded (steps 4..10 double the bits seven times), and
+        rescaled by q_{level+1}.  The 127 key switches' noise is divided by q with the bits, so
+        the keys come out with the rescale's rounding noise only (quieter than a fresh
+        encryption).  The element carries key-switch noise at indices that are no multiple of
+        16, which the steps mix instead of doubling, and Engine.expand's pre-scale by 2^-7 mod q
+        would turn that noise into full-size residues: the factor 2^7 is therefore multiplied in
+        beforehand, exactly, so that the pre-scale gives back the residues of C el word for word."""
+        e = self.e
+        if not 0 <= level < el.level or el.batch != 1:
+            raise ValueError(f"a key at level {level} needs its element (batch 1) at level > {level}")
+        amp = self.bundle_amplitude(bundle_level)
+        if level + 1 < el.level:
+            el = e.level_down(el, level + 1)
+            amp *= e.scales[level + 1] / e.scales[bundle_level]  # the level-down keeps the canonical scale
+        c = int(round(e.scales[level] * e.primes[level + 1] / (amp * (1 << self.BUNDLE_STAGE2))))
+        if c < 1 << 16:
+            raise ValueError("the chain's primes are too small for the bundle's amplitude")
+        x = e.expand(self._times(el, c << self.BUNDLE_STAGE2), xkeys[4:], first=4)
+        return e.rescale(x)
+
+    def expand_round_keys(self, bundle: Ciphertext, xkeys, levels) -> list:
+        """The bundle -> keys[k][r][j], batch 4, key k at levels[k]: the structure of
+        [encrypt_round_key(rk_k, levels[k]) for k]; keystream_aes128 / transcipher take it
+        unchanged.  Steps 0..3 give 16 elements, element k the coefficients of key k; elements
+        11..15 are dropped.  Each key's 128 elements are then expanded one level above that key's
+        own (expand_key_subtree), so that the peak is 128 elements at that key's limbs plus one."""
+        self._bundle_ring()
+        if len(xkeys) != 11 or len(levels) != 11:
+            raise ValueError("expand_round_keys takes 11 expansion keys and 11 levels")
+        if bundle.batch != 1 or max(levels) >= bundle.level:
+            raise ValueError(f"the bundle must be one ciphertext at level > {max(levels)}, one above the highest key")
+        by_key = self.e.expand(bundle, xkeys[:4], first=0)
+        keys = []
+        for k in range(11):
+            x = self.expand_key_subtree(self.e.slice(by_key, k, 1), xkeys, int(levels[k]), bundle.level)
+            keys.append([[self.e.slice(x, 4 * (r * 8 + j), 4) for j in range(8)] for r in range(4)])
+        return keys
+
     # ---- round steps --------------------------------------------------------------------------
     def key_mul(self, a: Ciphertext, k: Ciphertext) -> Ciphertext:
         """a XOR k: the batch-4 key (element c) against a's elements 4 s + c -- aesfhe_mul's cyclic

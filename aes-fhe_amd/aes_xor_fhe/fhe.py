@@ -822,6 +822,89 @@ class Engine:
             parts.append(self._call_ct(self._lib.mul_pt, el._h, pt._h))
         return self.concat(parts)
 
+    # -- coefficient expansion -------------------------------------------------
+    def encrypt_coefficients(self, coeffs, key, level: int | None = None) -> Ciphertext:
+        """Encrypt (B, N) int64 ring coefficients as they are (aesfhe_encrypt: no codec, no
+        scale), one batch element per row; a 1-D array is one element.  Same nonce sequence as
+        encrypt."""
+        level = self.max_level if level is None else int(level)
+        co = np.ascontiguousarray(coeffs, dtype=np.int64)
+        co = co[None] if co.ndim == 1 else co
+        if co.ndim != 2 or co.shape[1] != 1 << self.log_coeff_count:
+            raise ValueError(f"coefficients must be ({1 << self.log_coeff_count},) or (B, {1 << self.log_coeff_count})")
+        nonce = self._nonce
+        self._nonce += 1
+        return self._call_ct(self._lib.encrypt, key._h, _as_ptr(co, C.c_int64), co.shape[0], level, nonce)
+
+    def create_expansion_keys(self, sk: SecretKey, first: int, n: int) -> list:
+        """The galois keys of expansion steps first .. first + n - 1: g = N / 2^j + 1."""
+        first, n = int(first), int(n)
+        if first < 0 or n < 1 or first + n > self.log_coeff_count:
+            raise ValueError(f"expansion steps {first}..{first + n - 1} not within 0..{self.log_coeff_count - 1}")
+        N = 1 << self.log_coeff_count
+        return [self._galois_key(sk, (N >> j) + 1, GaloisKey) for j in range(first, first + n)]
+
+    def _monomial_shift(self, ct: Ciphertext, t: int) -> Ciphertext:
+        """ct * X^-t as a negacyclic shift in the coefficient domain: aesfhe_ntt_host back, the
+        coefficients moved down by t places with the wrapped tail negated, aesfhe_ntt_host
+        forward.  No multiplication (the checker's side of expand)."""
+        res = self.export_residues(ct)
+        B, P, nl, N = res.shape
+        flat = np.ascontiguousarray(res.reshape(B * P * nl, N))
+        pids = np.ascontiguousarray(np.arange(B * P * nl, dtype=np.int32) % nl)
+        self._check(self._lib.ntt_host(self._h, _as_ptr(flat, C.c_uint64), flat.shape[0], _as_ptr(pids, C.c_int32), 1))
+        q = np.array(self.primes[:nl], dtype=np.uint64)[pids][:, None]
+        flat = np.roll(flat, -t, axis=1)
+        tail = flat[:, N - t:]
+        flat[:, N - t:] = np.where(tail == 0, tail, q - tail)
+        flat = np.ascontiguousarray(flat)
+        self._check(self._lib.ntt_host(self._h, _as_ptr(flat, C.c_uint64), flat.shape[0], _as_ptr(pids, C.c_int32), 0))
+        return self.import_residues(flat.reshape(B, P, nl, N))
+
+    def expand(self, ct: Ciphertext, keys: Sequence[GaloisKey], first: int = 0) -> Ciphertext:
+        """Coefficient expansion, steps first .. first + len(keys) - 1: element
+        t * B0 + b of the result (batch B0 * 2^n, same level and scale) holds the coefficients of
+        ct's element b at the indices 2^first (t + 2^n w), unscaled, at index 2^(first + n) w.
+        keys: create_expansion_keys(sk, first, n).  The HIP engine runs aesfhe_expand; a backend
+        without include/aesfhe_ext.h (the CPU oracle, the checker of that path) runs the same
+        arithmetic through aesfhe.h: the pre-scale in Python integers on exported residues, then
+        per step galois, add, sub, the monomial as a coefficient-domain shift, concat."""
+        n, first = len(keys), int(first)
+        if self._lib.has_ext:
+            arr = (c_key_p * max(n, 1))(*[k._h for k in keys])
+            return self._call_ct(self._lib.expand, ct._h, first, n, arr)
+        if self.on_device:  # the product never takes the checker's path
+            raise RuntimeError(f"{self._lib.path}: the HIP engine lacks include/aesfhe_ext.h: rebuild it")
+        # aesfhe_expand's own refusals
+        bad = f"[{self._lib.backend}] invalid argument: "
+        if ct.npoly != 2:
+            raise RuntimeError(f"[{self._lib.backend}] degree error: Input ciphertext should have 2 polynomials")
+        if first < 0 or n < 1 or first + n > self.log_coeff_count:
+            raise RuntimeError(bad + f"expansion steps {first}..{first + n - 1} not within 0..{self.log_coeff_count - 1}")
+        N = 1 << self.log_coeff_count
+        for i, k in enumerate(keys):
+            kind, g = C.c_int32(), C.c_uint64()
+            self._check(self._lib.key_info(k._h, C.byref(kind), C.byref(g)))
+            if getattr(k, "engine", self) is not self or kind.value != 3:
+                raise RuntimeError(bad + f"expansion key {i} is not a galois key of this engine")
+            if g.value != (N >> (first + i)) + 1:
+                raise RuntimeError(bad + f"expansion key {i} has galois element {g.value}, step {first + i} needs "
+                                   f"{(N >> (first + i)) + 1}")
+        if (ct.batch << n) > 65535:
+            raise RuntimeError(bad + f"expanded batch {ct.batch << n} above 65535")
+        if ct.is_zero:
+            return self.zeros(ct.batch << n, ct.level)
+        res = self.export_residues(ct).astype(object)
+        for i in range(ct.level + 1):
+            q = self.primes[i]
+            res[:, :, i] = (res[:, :, i] * pow(1 << n, -1, q)) % q
+        c = self.import_residues(res.astype(np.uint64))
+        for i, k in enumerate(keys):
+            u = self._call_ct(self._lib.galois, c._h, k._h)
+            s, d = self._call_ct(self._lib.add, c._h, u._h), self._call_ct(self._lib.sub, c._h, u._h)
+            c = self.concat([s, self._monomial_shift(d, 1 << (first + i))])
+        return c
+
     # -- deferred linear combinations (_LinearCiphertext) -------------------------------------
     def _linear_add(self, a, b):
         """a + b with at least one deferred operand: the merged deferred sum, or None when b is

@@ -11,6 +11,11 @@
  * per element, aesfhe_ct_slice + aesfhe_pt_create + aesfhe_mul_pt, then aesfhe_ct_concat, which
  * is also what the CPU oracle runs as the checker (Engine.multiply_plain_batch's fallback).
  *
+ * Also here: the coefficient expansion (aesfhe_expand below), which unpacks the coefficients of
+ * one ciphertext into one ciphertext each -- what lets a transciphering client upload its AES
+ * round keys as a single ciphertext.  It needs an exact, level-free product with a monomial, which
+ * aesfhe.h does not offer on the device; the oracle's facade path shifts coefficients on the host.
+ *
  * Only libaesfhe.so (HIP, gfx950) exports these; the oracle does not, and AESFHE_ABI_VERSION is
  * unchanged.  Conventions (error codes, handles, aesfhe_last_error) are those of aesfhe.h.
  */
@@ -44,6 +49,24 @@ void aesfhe_ptb_free(aesfhe_ptb *ptb);
  * AESFHE_ELEVEL; a zero ciphertext gives a zero ciphertext. */
 int aesfhe_mul_ptb(aesfhe_engine *eng, const aesfhe_ct *ct, const aesfhe_ptb *ptb,
                    aesfhe_ct **out);
+
+/* Coefficient expansion: steps j = first_step .. first_step + n_steps - 1
+ * of the unpacking that separates the coefficients of a 2-polynomial ciphertext by the residue of
+ * their index, first_step >= 0, n_steps >= 1, first_step + n_steps <= logN.  Every residue is first
+ * multiplied by (2^n_steps)^-1 mod q_i; then, with B the current batch and u the automorphism of c
+ * under keys[j - first_step] (word for word aesfhe_galois' result, g = N / 2^j + 1), a step
+ * doubles the batch: out[b] = c[b] + u[b], out[B + b] = (c[b] - u[b]) * X^(-2^j).  Element
+ * t * batch + b of the result holds the coefficients of input element b at the indices
+ * 2^first_step * (t + 2^n_steps * w), unscaled, at index 2^(first_step + n_steps) * w (those at
+ * indices that are no multiple of 2^first_step must already be zero, as after the steps below
+ * first_step).  Level and scale are unchanged: no level is consumed.
+ * keys[i]: a galois key (aesfhe_key_galois, kind 3) of element N / 2^(first_step + i) + 1, stored
+ * digits enough for ct's level; anything else is AESFHE_EARG (a trimmed key: AESFHE_ELEVEL), as
+ * are a step range outside the ring's and a result batch above 65535.  npoly != 2 is
+ * AESFHE_EDEGREE.  A zero ciphertext gives a zero ciphertext of batch * 2^n_steps elements.  A
+ * refused call takes no device memory and enqueues nothing. */
+int aesfhe_expand(aesfhe_engine *eng, const aesfhe_ct *ct, int32_t first_step, int32_t n_steps,
+                  const aesfhe_key *const *keys, aesfhe_ct **out);
 
 #ifdef __cplusplus
 }
