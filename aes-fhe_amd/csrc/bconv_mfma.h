@@ -19,6 +19,7 @@
 // oracle) rides in one more byte slot of K whose constant column is -D mod q_i.
 #pragma once
 #include "kernels.h"
+#include "basis_tables.h"  // kBconvKT: K bytes per table row (up to 4 MFMA steps of 32)
 
 namespace aesfhe {
 
@@ -47,7 +48,6 @@ struct BconvArgs {
     const double* qinvall;
     int tiles_per_group;   // target tiles (4 targets) per blockIdx.y
 };
-constexpr int kBconvKT = 128;  // K bytes per table row (up to 4 MFMA steps of 32)
 
 // (x, y) -> (x with lanes 32..63 taken from y's lanes 0..31, y with lanes 0..31 taken from x's
 // lanes 32..63): v_permlane32_swap on both dwords of the doubles

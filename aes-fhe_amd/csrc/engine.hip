@@ -26,6 +26,7 @@
 #include "ks_fused.h"
 #include "bconv_mfma.h"
 #include "bconv_cols.h"
+#include "basis_tables.h"
 #include "bsgs_plan.h"
 #include "operands.h"
 #include "arena.h"
@@ -123,6 +124,30 @@ struct Pool : Arena {
     }
 };
 
+// The device blocks that live as long as the engine: every table of build_tables and the codec's.
+struct HipFree {
+    void operator()(void* p) const { hipFree(p); }
+};
+struct DevBlocks {
+    std::vector<std::unique_ptr<void, HipFree>> blocks;
+    void* get(size_t bytes) {
+        blocks.reserve(blocks.size() + 1);  // no throw between hipMalloc and the record
+        void* p = nullptr;
+        HIPC(hipMalloc(&p, std::max<size_t>(bytes, 8)));
+        blocks.emplace_back(p);
+        return p;
+    }
+    template <typename T>
+    T* up(const std::vector<T>& v) {
+        T* d = (T*)get(v.size() * sizeof(T));
+        HIPC(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return d;
+    }
+    void drop(void* p) {  // a block that is replaced (the codec's flags when a batch outgrows them)
+        blocks.erase(std::remove_if(blocks.begin(), blocks.end(), [p](const auto& b) { return b.get() == p; }), blocks.end());
+    }
+};
+
 struct ProfRec {
     int fam;
     hipEvent_t a, b;
@@ -136,48 +161,51 @@ struct KernStat {  // per kernel class (aesfhe_engine_profile_kernels)
     double ms = 0, bytes = 0;
 };
 
+// The tables of a ModDown by D = P q_l ... q_{l-r+1}: plain (r = 0, one cell for every level) or
+// combined with r rescales.  The engine's `md` points at cell 0 of each table, md_tabs(e, l, r) at
+// cell md_cell(Lp1, r, l) (basis_tables.h).
+struct MdTabs {
+    const double *invf, *ninvf, *einv;  // per source j: (D/e_j)^{-1} / e_j, the same times N^{-1}, 1 / e_j
+    const int8_t* tab;                  // matrix-core rows and corrections per target (bconv_mfma.h)
+    const double* corr;
+    const u64* dinv;                    // D^{-1} mod q_i per target, and as w / q for the finish
+    const double* dinvf;
+    const TwD* hatf;                    // k_moddown: (D/e_j) mod q_i, rows kMdrMaxE wide; D mod q_i as w / q
+    const double* dmodf;
+};
+
 struct aesfhe_engine {
     // one reference for the engine handle plus one per live ct / pt / key: the tables, pool and
     // stream outlive aesfhe_engine_destroy until the last object is freed (Python's cycle
     // collector finalises an engine and its ciphertexts in arbitrary order)
     std::atomic<int> refs{1};
     int logN, N, L, K, A, dnum, np, Lp1;  // A: key-switch digit width (alpha)
-    int device;
+    int device = 0;
     u64 seed;
     ChaKey ck;  // ChaCha20 key of every random stream
     Chain chain;
-    hipStream_t stream;
+    hipStream_t stream = nullptr;
     // one arena for every block (`tpool` is unused): a second arena for the per-call temporaries
     // (tried in round 5 against the holes short-lived blocks leave between long-lived ones) held
     // more in the replay of the bench's block events (tools/arena_replay.cpp: bench round 1.28 vs
     // 1.26 x its peak live set, config 5 249 vs 236 GB)
     Pool pool, tpool;
     size_t peak_total = 0;  // largest pool.live + tpool.live seen
-    // device tables
-    u64 *q, *psi, *ipsi, *ninv;
-    double *qinv, *psif, *ipsif, *ninvf;
-    double *rtwf = nullptr, *irtwf = nullptr;  // N = 2^16 row-pass twiddle factors [np][256][8] (ntt256f.h)
-    Tw *tw, *itw;
-    double *cw = nullptr, *icw = nullptr;  // [np][kColW] uniform column-stage twiddles w (kernels.h)
-    u64* iroot;  // host copy only needed
-    std::vector<u64> h_iroot;
-    // base conversion tables
-    u64 *mu_hatinv, *mu_hat, *md_phatinv, *md_phat, *md_pinv, *rs_inv, *rs_mod, *pmod;
-    // combined ModDown + rescale (drop r = 1, 2 top Q primes with P), see build_tables
-    double *mdr_invf = nullptr, *mdr_dinvf = nullptr, *pmodf = nullptr;
-    TwD* mdr_hatf = nullptr;  // {w, w/q}
-    double *mdr_einv = nullptr, *mdr_dmodf = nullptr, *md_einv = nullptr;
-    u64* mdr_dinv = nullptr;
-    double *mu_hatinvf, *md_phatinvf, *md_pinvf, *rs_invf;
-    double* mu_nhatf = nullptr;  // [level l][limb i] N^{-1} hatinv_{l,i} / q_i: the INTT before a fused ModUp
-    // the same for a fused ModDown's sources: N^{-1} (D/e_j)^{-1} / e_j, plain ([kMdrMaxE]) and
-    // combined with r rescales ([cell][kMdrMaxE], as mdr_invf)
-    double *md_ninvf = nullptr, *mdr_ninvf = nullptr;
-    TwD* md_phatf;  // ModDown base-conversion constants {w, w/q} (k_moddown)
-    // matrix-core base conversions (bconv_mfma.h): [set / cell][pid][8 planes][kBconvKT] signed
-    // bytes, the XOR-0x80 corrections [set / cell][pid] and (2^32 mod p) / p per prime
-    int8_t *bc_mu_tab = nullptr, *bc_md_tab = nullptr, *bc_mdr_tab = nullptr;
-    double *bc_mu_corr = nullptr, *bc_md_corr = nullptr, *bc_mdr_corr = nullptr, *bc_pc = nullptr;
+    // device tables: `dev` owns every block, the fields below point into them
+    DevBlocks dev;
+    u64* q;
+    double* qinv;
+    Tabs tab{};  // what the NTT kernels take (kernels.h), assembled once by build_tables
+    std::vector<u64> h_iroot;  // psi^{N/2} per prime, host only (poly2 constants)
+    // base conversion tables (basis_tables.h): ModUp sets, ModDown cells md_cell(Lp1, r, l), rescale
+    double *mu_hatinvf, *mu_nhatf, *rs_invf;
+    MdTabs md;
+    u64 *pmod, *rs_inv, *rs_mod;
+    const double* pmodf;  // the r = 0 cell's dmodf, (P mod q_i) / q_i of the row kernels
+    // matrix-core base conversions (bconv_mfma.h): [set / cell][pid / target][8 planes][kBconvKT]
+    // signed bytes, the XOR-0x80 corrections beside them and (2^32 mod p) / p per prime
+    int8_t* bc_mu_tab;
+    double *bc_mu_corr, *bc_pc;
     // small-argument upload ring (device) + pinned staging
     char* ring_d = nullptr;
     char* ring_h = nullptr;
@@ -198,25 +226,26 @@ struct aesfhe_engine {
     int64_t prof_n[4] = {0, 0, 0, 0};
     std::map<std::string, KernStat> prof_k;
 
-    Tabs tabs() const {
-        Tabs t;
-        t.q = q;
-        t.qinv = qinv;
-        t.psi = psi;
-        t.psif = psif;
-        t.ipsi = ipsi;
-        t.ipsif = ipsif;
-        t.rtwf = rtwf;
-        t.irtwf = irtwf;
-        t.ninv = ninv;
-        t.ninvf = ninvf;
-        t.tw = tw;
-        t.itw = itw;
-        t.cw = cw;
-        t.icw = icw;
-        t.logN = logN;
-        t.Lp1 = Lp1;
-        return t;
+    const Tabs& tabs() const { return tab; }
+
+    // Everything the engine holds on the device, in any state aesfhe_engine_create can leave it;
+    // nothing exists there before the stream does.  `dev` frees the tables after this body.
+    ~aesfhe_engine() {
+        if (!stream) return;
+        hipSetDevice(device);
+        hipStreamSynchronize(stream);
+        for (auto& r : recs) {
+            hipEventDestroy(r.a);
+            hipEventDestroy(r.b);
+        }
+        for (auto ev : spare) hipEventDestroy(ev);
+        pool.release_all();
+        tpool.release_all();
+        if (pool.trace) fclose(pool.trace);
+        for (auto& kv : poly2_tabs) hipFree(kv.second);
+        if (ring_d) hipFree(ring_d);
+        if (ring_h) hipHostFree(ring_h);
+        hipStreamDestroy(stream);
     }
 };
 
@@ -248,7 +277,6 @@ struct aesfhe_pt {
 // -----------------------------------------------------------------------------------------------
 // helpers
 static const int FAM_NTT = 0, FAM_KS = 1, FAM_EW = 2;
-static const int kMdrMaxR = 2, kMdrMaxE = 16;  // combined ModDown + rescale: r <= 2, K + r <= 16
 
 struct ProfScope {
     aesfhe_engine* e;
@@ -603,41 +631,6 @@ static Span span_s(u64* base, long pstride, int nl, int nq, int qpid0, int spid0
 // -----------------------------------------------------------------------------------------------
 // engine creation: tables
 
-// bytes of a canonical residue of prime q (0 <= y < q)
-static int res_bytes(u64 q) {
-    int b = 0;
-    for (u64 x = q - 1; x; x >>= 8) b++;
-    return b;
-}
-// The constant rows of one target prime p for a matrix-core base conversion (bconv_mfma.h):
-// tab = 8 planes x kBconvKT bytes; source slot sl's byte a (K byte 8 sl + a) holds the signed
-// balanced base-256 digits of H' = 256^a H[sl] mod p over the planes b = 0..6 (plane 7 zero), for
-// the bytes a < res_bytes(q_sl) a canonical y can have; with vc, K byte 8 ns holds those of G
-// (ModDown's -D mod p, times the in-kernel v).  Returns 128 * (sum of every H' placed) mod p:
-// the kernel feeds the bytes as u - 128 (XOR 0x80, signed MFMA operands).
-static u64 bconv_row(int8_t* tab, u64 p, int ns, const u64* srcq, const u64* H, bool vc, u64 G) {
-    u64 corr = 0;
-    auto place = [&](int k, u64 hp) {
-        int64_t x = (int64_t)hp;  // < 2^50: seven balanced digits reach 2^55
-        for (int b = 0; b < 7; b++) {
-            const int d = (int)((x + 128) & 255) - 128;
-            tab[b * kBconvKT + k] = (int8_t)d;
-            x = (x - d) / 256;
-        }
-        if (x != 0) throw_err(AESFHE_EUNSUPPORTED, "base-conversion constant beyond 7 bytes");
-        corr = (corr + h_mulmod(128 % p, hp, p)) % p;
-    };
-    for (int sl = 0; sl < ns; sl++) {
-        u64 r = 1 % p;  // 256^a mod p
-        for (int a = 0; a < res_bytes(srcq[sl]); a++) {
-            place(8 * sl + a, h_mulmod(r, H[sl] % p, p));
-            r = h_mulmod(r, 256 % p, p);
-        }
-    }
-    if (vc) place(8 * ns, G % p);
-    return corr;
-}
-
 static void build_tables(aesfhe_engine* e) {
     const int N = e->N, np = e->np, L = e->L, K = e->K, Lp1 = e->Lp1;
     const auto& Q = e->chain.q;
@@ -665,20 +658,16 @@ static void build_tables(aesfhe_engine* e) {
         hninv[p] = h_invmod((u64)N, qq);
         hninvf[p] = (double)hninv[p] / (double)qq;
     }
-    auto up = [&](auto& vec, auto** dst) {
-        using T = typename std::remove_reference<decltype(vec)>::type::value_type;
-        size_t bytes = vec.size() * sizeof(T);
-        HIPC(hipMalloc((void**)dst, std::max<size_t>(bytes, 8)));
-        HIPC(hipMemcpy(*dst, vec.data(), bytes, hipMemcpyHostToDevice));
-    };
-    up(hq, &e->q);
-    up(hqinv, &e->qinv);
-    up(hpsi, &e->psi);
-    up(hpsif, &e->psif);
-    up(hipsi, &e->ipsi);
-    up(hipsif, &e->ipsif);
-    up(hninv, &e->ninv);
-    up(hninvf, &e->ninvf);
+    DevBlocks& dev = e->dev;
+    Tabs& t = e->tab;
+    t.q = e->q = dev.up(hq);
+    t.qinv = e->qinv = dev.up(hqinv);
+    t.psi = dev.up(hpsi);
+    t.psif = dev.up(hpsif);
+    t.ipsi = dev.up(hipsi);
+    t.ipsif = dev.up(hipsif);
+    t.ninv = dev.up(hninv);
+    t.ninvf = dev.up(hninvf);
     if (fused_ntt(e)) {  // row factors psi^{+-brv(row << s)} / q, s = 0..7, [np][R][8] (ntt256f.h tw_row)
         const int R = N / 256;
         std::vector<double> hr((size_t)np * R * 8), hir((size_t)np * R * 8);
@@ -688,8 +677,8 @@ static void build_tables(aesfhe_engine* e) {
                     hr[((size_t)p * R + row) * 8 + sh] = hpsif[(size_t)p * N + (row << sh)];
                     hir[((size_t)p * R + row) * 8 + sh] = hipsif[(size_t)p * N + (row << sh)];
                 }
-        up(hr, &e->rtwf);
-        up(hir, &e->irtwf);
+        t.rtwf = dev.up(hr);
+        t.irtwf = dev.up(hir);
     }
     {
         std::vector<Tw> htw((size_t)np * N), hitw((size_t)np * N);
@@ -697,8 +686,8 @@ static void build_tables(aesfhe_engine* e) {
             htw[i] = Tw{hpsi[i], hpsif[i]};
             hitw[i] = Tw{hipsi[i], hipsif[i]};
         }
-        up(htw, &e->tw);
-        up(hitw, &e->itw);
+        t.tw = dev.up(htw);
+        t.itw = dev.up(hitw);
     }
     {
         std::vector<double> hcw((size_t)np * kColW), hicw((size_t)np * kColW);
@@ -707,213 +696,31 @@ static void build_tables(aesfhe_engine* e) {
                 hcw[(size_t)p * kColW + k] = (double)hpsi[(size_t)p * N + (k < N ? k : 0)];
                 hicw[(size_t)p * kColW + k] = (double)hipsi[(size_t)p * N + (k < N ? k : 0)];
             }
-        up(hcw, &e->cw);
-        up(hicw, &e->icw);
+        t.cw = dev.up(hcw);
+        t.icw = dev.up(hicw);
     }
+    t.logN = e->logN;
+    t.Lp1 = Lp1;
 
-    // ModUp tables per (digit j, width a <= alpha): hatinv[i], hat[i][pid]; stride A = alpha
-    const int A = e->A;
-    const size_t mu_sets = (size_t)e->dnum * A;
-    std::vector<u64> hhatinv(mu_sets * A, 0), hhat(mu_sets * A * np, 0);
-    std::vector<double> hhatinvf(mu_sets * A, 0);
-    for (int j = 0; j < e->dnum; j++)
-        for (int a = 1; a <= A; a++) {
-            int lo = j * A, hi = lo + a;
-            if (hi > Lp1) continue;
-            size_t set = (size_t)j * A + (a - 1);
-            for (int i = lo; i < hi; i++) {
-                u64 prod = 1;
-                for (int i2 = lo; i2 < hi; i2++)
-                    if (i2 != i) prod = h_mulmod(prod, Q[i2] % Q[i], Q[i]);
-                u64 hv = h_invmod(prod, Q[i]);
-                hhatinv[set * A + (i - lo)] = hv;
-                hhatinvf[set * A + (i - lo)] = (double)hv / (double)Q[i];
-                for (int pid = 0; pid < np; pid++) {
-                    u64 qt = Q[pid], h = 1;
-                    for (int i2 = lo; i2 < hi; i2++)
-                        if (i2 != i) h = h_mulmod(h, Q[i2] % qt, qt);
-                    hhat[(set * A + (i - lo)) * np + pid] = h;
-                }
-            }
-        }
-    up(hhatinv, &e->mu_hatinv);
-    up(hhatinvf, &e->mu_hatinvf);
-    {  // the INTT in front of a fused ModUp (bconv_cols.h YIN) scales limb i of a level-l input by
-       // N^{-1} hatinv_{l,i} (its digit's width at level l) instead of N^{-1}: it emits y directly
-        std::vector<double> nh((size_t)Lp1 * Lp1, 0.0);
-        for (int l = 0; l < Lp1; l++)
-            for (int i = 0; i <= l; i++) {
-                const int lo = (i / A) * A, a = std::min(A, l + 1 - lo);
-                const u64 hv = hhatinv[((size_t)(i / A) * A + (a - 1)) * A + (i - lo)];
-                nh[(size_t)l * Lp1 + i] = (double)h_mulmod(hninv[i], hv, Q[i]) / (double)Q[i];
-            }
-        up(nh, &e->mu_nhatf);
-    }
-    up(hhat, &e->mu_hat);
-    {  // matrix-core ModUp rows: [set][pid] (the digit's own pids are never targets)
-        const size_t row = 8 * (size_t)kBconvKT;
-        std::vector<int8_t> tab(mu_sets * np * row, 0);
-        std::vector<double> corr(mu_sets * np, 0.0), pc(4 * (size_t)np);
-        for (int j = 0; j < e->dnum; j++)
-            for (int a = 1; a <= A; a++) {
-                const int lo = j * A;
-                if (lo + a > Lp1 || a > 16) continue;
-                const size_t set = (size_t)j * A + (a - 1);
-                for (int pid = 0; pid < np; pid++) {
-                    std::vector<u64> H(a);
-                    for (int i = 0; i < a; i++) H[i] = hhat[(set * A + i) * np + pid];
-                    corr[set * np + pid] = (double)bconv_row(&tab[(set * np + pid) * row], Q[pid], a, &Q[lo], H.data(), false, 0);
-                }
-            }
-        for (int pid = 0; pid < np; pid++) {  // {p, 1/p, 2^32 mod p, (2^32 mod p) / p}
-            const u64 p = Q[pid], w = (1ULL << 32) % p;
-            pc[4 * pid] = (double)p;
-            pc[4 * pid + 1] = 1.0 / (double)p;
-            pc[4 * pid + 2] = (double)w;
-            pc[4 * pid + 3] = (double)w / (double)p;
-        }
-        up(tab, &e->bc_mu_tab);
-        up(corr, &e->bc_mu_corr);
-        up(pc, &e->bc_pc);
-    }
-
-    // ModDown tables
-    std::vector<u64> hphatinv(K), hphat((size_t)K * Lp1), hpinv(Lp1), hpmod(np, 0);
-    std::vector<double> hphatinvf(K), hpinvf(Lp1);
-    std::vector<TwD> hphatf((size_t)K * Lp1);
-    for (int k = 0; k < K; k++) {
-        u64 pk = Q[Lp1 + k], prod = 1;
-        for (int k2 = 0; k2 < K; k2++)
-            if (k2 != k) prod = h_mulmod(prod, Q[Lp1 + k2] % pk, pk);
-        hphatinv[k] = h_invmod(prod, pk);
-        hphatinvf[k] = (double)hphatinv[k] / (double)pk;
-        for (int i = 0; i < Lp1; i++) {
-            u64 qi = Q[i], h = 1;
-            for (int k2 = 0; k2 < K; k2++)
-                if (k2 != k) h = h_mulmod(h, Q[Lp1 + k2] % qi, qi);
-            hphat[(size_t)k * Lp1 + i] = h;
-            hphatf[(size_t)i * K + k] = TwD{(double)h, (double)h / (double)qi};  // [target i][source k]
-        }
-    }
-    for (int i = 0; i < Lp1; i++) {
-        u64 qi = Q[i], P = 1;
-        for (int k = 0; k < K; k++) P = h_mulmod(P, Q[Lp1 + k] % qi, qi);
-        hpmod[i] = P;
-        hpinv[i] = h_invmod(P, qi);
-        hpinvf[i] = (double)hpinv[i] / (double)qi;
-    }
-    {  // matrix-core ModDown rows, r = 0: sources p_0..p_{K-1}, targets q_i, v slot G = -P mod q_i
-        const size_t row = 8 * (size_t)kBconvKT;
-        std::vector<int8_t> tab((size_t)Lp1 * row, 0);
-        std::vector<double> corr(Lp1, 0.0);
-        if (K + 1 <= 16)
-            for (int i = 0; i < Lp1; i++) {
-                const u64 qi = Q[i];
-                std::vector<u64> H(K);
-                u64 P = 1;
-                for (int k = 0; k < K; k++) {
-                    H[k] = hphat[(size_t)k * Lp1 + i];
-                    P = h_mulmod(P, Q[Lp1 + k] % qi, qi);
-                }
-                corr[i] = (double)bconv_row(&tab[(size_t)i * row], qi, K, &Q[Lp1], H.data(), true, (qi - P) % qi);
-            }
-        up(tab, &e->bc_md_tab);
-        up(corr, &e->bc_md_corr);
-    }
-    up(hphatinv, &e->md_phatinv);
-    up(hphatinvf, &e->md_phatinvf);
-    up(hphat, &e->md_phat);
-    up(hphatf, &e->md_phatf);
-    up(hpinv, &e->md_pinv);
-    up(hpinvf, &e->md_pinvf);
-    up(hpmod, &e->pmod);
-    {
-        std::vector<double> hpmodf(Lp1);
-        for (int i = 0; i < Lp1; i++) hpmodf[i] = (double)hpmod[i] / (double)Q[i];
-        up(hpmodf, &e->pmodf);
-        std::vector<double> heinv0(kMdrMaxE, 0.0);  // 1/p_k: the exact conversion of plain ModDown
-        for (int k = 0; k < K; k++) heinv0[k] = 1.0 / (double)Q[Lp1 + k];
-        up(heinv0, &e->md_einv);
-        std::vector<double> hn0(kMdrMaxE, 0.0);  // fused ModDown: N^{-1} phatinv_k folded into the INTT
-        for (int k = 0; k < K; k++) hn0[k] = (double)h_mulmod(hninv[Lp1 + k], hphatinv[k], Q[Lp1 + k]) / (double)Q[Lp1 + k];
-        up(hn0, &e->md_ninvf);
-    }
-    // combined ModDown + rescale: E = {q_{l-r+1}..q_l, p_0..p_{K-1}} (acc limb order), D = prod E
-    //   mdr_invf[(r-1, l)][j]       = (D/e_j)^{-1} mod e_j, as w/e_j
-    //   mdr_hatf[(r-1, l)][i][j]    = (D/e_j) mod q_i, as {w, w/q_i}   (i <= l - r)
-    //   mdr_dinv[(r-1, l)][i] (+f)  = D^{-1} mod q_i
-    {
-        const size_t cells = (size_t)kMdrMaxR * Lp1;
-        std::vector<double> hinvf(cells * kMdrMaxE, 0.0), hdinvf(cells * Lp1, 0.0);
-        std::vector<TwD> hhatf(cells * kMdrMaxE * Lp1, TwD{0, 0});
-        std::vector<u64> hdinv(cells * Lp1, 0);
-        std::vector<double> heinv(cells * kMdrMaxE, 0.0), hdmodf(cells * Lp1, 0.0), hninvf(cells * kMdrMaxE, 0.0);
-        // matrix-core rows [cell][target i][8][kBconvKT] (bconv_mfma.h), v slot G = -D mod q_i
-        const size_t brow = 8 * (size_t)kBconvKT;
-        std::vector<int8_t> btab(cells * Lp1 * brow, 0);
-        std::vector<double> bcorr(cells * Lp1, 0.0);
-        for (int r = 1; r <= kMdrMaxR && K + r <= kMdrMaxE; r++)
-            for (int l = r; l <= L; l++) {
-                const size_t cell = (size_t)(r - 1) * Lp1 + l;
-                std::vector<int> E;
-                for (int j = 0; j < r; j++) E.push_back(l - r + 1 + j);
-                for (int j = 0; j < K; j++) E.push_back(Lp1 + j);
-                std::vector<u64> Hc((size_t)(l - r + 1) * E.size()), Eq(E.size());
-                for (size_t j = 0; j < E.size(); j++) Eq[j] = Q[E[j]];
-                for (size_t j = 0; j < E.size(); j++) {
-                    const u64 ej = Q[E[j]];
-                    u64 prod = 1;
-                    for (size_t j2 = 0; j2 < E.size(); j2++)
-                        if (j2 != j) prod = h_mulmod(prod, Q[E[j2]] % ej, ej);
-                    hinvf[cell * kMdrMaxE + j] = (double)h_invmod(prod, ej) / (double)ej;
-                    hninvf[cell * kMdrMaxE + j] = (double)h_mulmod(hninv[E[j]], h_invmod(prod, ej), ej) / (double)ej;
-                    heinv[cell * kMdrMaxE + j] = 1.0 / (double)ej;
-                    for (int i = 0; i <= l - r; i++) {
-                        const u64 qi = Q[i];
-                        u64 h = 1;
-                        for (size_t j2 = 0; j2 < E.size(); j2++)
-                            if (j2 != j) h = h_mulmod(h, Q[E[j2]] % qi, qi);
-                        hhatf[(cell * Lp1 + i) * kMdrMaxE + j] = TwD{(double)h, (double)h / (double)qi};  // [cell][target i][source j]
-                        Hc[(size_t)i * E.size() + j] = h;
-                    }
-                }
-                for (int i = 0; i <= l - r; i++) {
-                    const u64 qi = Q[i];
-                    u64 D = 1;
-                    for (int ei : E) D = h_mulmod(D, Q[ei] % qi, qi);
-                    const u64 di = h_invmod(D, qi);
-                    hdinv[cell * Lp1 + i] = di;
-                    hdmodf[cell * Lp1 + i] = (double)D / (double)qi;
-                    hdinvf[cell * Lp1 + i] = (double)di / (double)qi;
-                    if ((int)E.size() + 1 <= 16)
-                        bcorr[cell * Lp1 + i] = (double)bconv_row(&btab[(cell * Lp1 + i) * brow], qi, (int)E.size(), Eq.data(),
-                                                                  &Hc[(size_t)i * E.size()], true, (qi - D) % qi);
-                }
-            }
-        up(btab, &e->bc_mdr_tab);
-        up(bcorr, &e->bc_mdr_corr);
-        up(hinvf, &e->mdr_invf);
-        up(hninvf, &e->mdr_ninvf);
-        up(hhatf, &e->mdr_hatf);
-        up(hdinv, &e->mdr_dinv);
-        up(hdinvf, &e->mdr_dinvf);
-        up(heinv, &e->mdr_einv);
-        up(hdmodf, &e->mdr_dmodf);
-    }
-
-    // rescale tables rs_inv[l][i] = q_l^{-1} mod q_i, rs_mod[l][i] = q_l mod q_i
-    std::vector<u64> hrinv((size_t)Lp1 * Lp1, 0), hrmod((size_t)Lp1 * Lp1, 0);
-    std::vector<double> hrinvf((size_t)Lp1 * Lp1, 0);
-    for (int l = 1; l <= L; l++)
-        for (int i = 0; i < l; i++) {
-            u64 qi = Q[i];
-            hrmod[(size_t)l * Lp1 + i] = Q[l] % qi;
-            hrinv[(size_t)l * Lp1 + i] = h_invmod(Q[l] % qi, qi);
-            hrinvf[(size_t)l * Lp1 + i] = (double)hrinv[(size_t)l * Lp1 + i] / (double)qi;
-        }
-    up(hrinv, &e->rs_inv);
-    up(hrinvf, &e->rs_invf);
-    up(hrmod, &e->rs_mod);
+    // base conversions (basis_tables.h): the vectors go up as built
+    static_assert(sizeof(WQ) == sizeof(TwD), "ModDown's hatf rows are the kernels' TwD");
+    ModUpTables mu;
+    ModDownTables md;
+    if (!build_modup_tables(Q, Lp1, e->A, hninv, mu) || !build_moddown_tables(Q, Lp1, e->K, hninv, md))
+        throw_err(AESFHE_EUNSUPPORTED, "base-conversion constant beyond 7 bytes");
+    e->mu_hatinvf = dev.up(mu.hatinvf);
+    e->mu_nhatf = dev.up(mu.nhatf);
+    e->bc_mu_tab = dev.up(mu.tab);
+    e->bc_mu_corr = dev.up(mu.corr);
+    e->bc_pc = dev.up(mu.pc);
+    e->md = MdTabs{dev.up(md.invf), dev.up(md.ninvf), dev.up(md.einv), dev.up(md.tab), dev.up(md.corr),
+                   dev.up(md.dinv), dev.up(md.dinvf), (TwD*)dev.up(md.hatf), dev.up(md.dmodf)};
+    e->pmod = dev.up(md.pmod);
+    e->pmodf = e->md.dmodf;  // cell 0
+    const RescaleTables rs = build_rescale_tables(Q, Lp1);
+    e->rs_inv = dev.up(rs.inv);
+    e->rs_invf = dev.up(rs.invf);
+    e->rs_mod = dev.up(rs.mod);
 }
 
 extern "C" int aesfhe_engine_create(const aesfhe_params* pp, aesfhe_engine** out) {
@@ -925,6 +732,8 @@ extern "C" int aesfhe_engine_create(const aesfhe_params* pp, aesfhe_engine** out
         throw_err(AESFHE_EARG, "bad level / special prime count");
     if (pp->scale_bits < 20 || pp->scale_bits > 50 || pp->base_bits > 50 || pp->special_bits > 50)
         throw_err(AESFHE_EARG, "bit sizes must keep every prime below 2^50");
+    // a throw below (a table or the ring refused by a full device) releases the stream, the tables
+    // and the ring: ~aesfhe_engine
     std::unique_ptr<aesfhe_engine> e(new aesfhe_engine());
     e->logN = pp->log_n;
     e->N = 1 << pp->log_n;
@@ -984,39 +793,11 @@ extern "C" int aesfhe_chain(const aesfhe_params* pp, uint64_t* primes, double* s
     API_END
 }
 
-static void engine_teardown(aesfhe_engine* e);
 static void engine_unref(aesfhe_engine* e) {
-    if (--e->refs == 0) engine_teardown(e);
+    if (--e->refs == 0) delete e;  // ~aesfhe_engine releases the device
 }
 extern "C" void aesfhe_engine_destroy(aesfhe_engine* e) {
     if (e) engine_unref(e);
-}
-static void engine_teardown(aesfhe_engine* e) {
-    hipSetDevice(e->device);
-    hipStreamSynchronize(e->stream);
-    for (auto& r : e->recs) {
-        hipEventDestroy(r.a);
-        hipEventDestroy(r.b);
-    }
-    for (auto ev : e->spare) hipEventDestroy(ev);
-    e->pool.release_all();
-    e->tpool.release_all();
-    if (e->pool.trace) fclose(e->pool.trace);
-    void* ptrs[] = {e->q, e->psi, e->ipsi, e->ninv, e->qinv, e->psif, e->ipsif, e->ninvf, e->rtwf, e->irtwf,
-                    e->mu_hatinv, e->mu_hat, e->md_phatinv, e->md_phat, e->md_pinv, e->rs_inv,
-                    e->rs_mod, e->pmod, e->mu_hatinvf, e->md_phatinvf, e->md_phatf,
-                    e->md_pinvf, e->rs_invf, e->ring_d, e->tw, e->itw, e->mdr_invf, e->mdr_hatf,
-                    e->mdr_dinv, e->mdr_dinvf, e->pmodf, e->mdr_einv, e->mdr_dmodf, e->md_einv,
-                    e->bc_mu_tab, e->bc_md_tab, e->bc_mdr_tab, e->bc_mu_corr, e->bc_md_corr, e->bc_mdr_corr,
-                    e->bc_pc, e->mu_nhatf, e->md_ninvf, e->mdr_ninvf, e->cw, e->icw};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    for (auto& kv : e->poly2_tabs) hipFree(kv.second);
-    for (void* p : {(void*)e->ckre, (void*)e->ckim, (void*)e->crot, (void*)e->cflags})
-        if (p) hipFree(p);
-    if (e->ring_h) hipHostFree(e->ring_h);
-    hipStreamDestroy(e->stream);
-    delete e;
 }
 
 extern "C" int aesfhe_engine_dims(const aesfhe_engine* e, int32_t d[4]) {
@@ -1663,12 +1444,9 @@ static CodecTabs codec_tabs(aesfhe_engine* e) {
     const long M = 2L * e->N;
     if (!e->ckre) {
         Codec c(e->logN);  // host twiddles (libm cos / sin): the device tables are the same doubles
-        HIPC(hipMalloc(&e->ckre, (M + 1) * sizeof(double)));
-        HIPC(hipMalloc(&e->ckim, (M + 1) * sizeof(double)));
-        HIPC(hipMalloc(&e->crot, n * sizeof(long)));
-        HIPC(hipMemcpy(e->ckre, c.kre.data(), (M + 1) * sizeof(double), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(e->ckim, c.kim.data(), (M + 1) * sizeof(double), hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(e->crot, c.rot.data(), n * sizeof(long), hipMemcpyHostToDevice));
+        e->ckre = e->dev.up(c.kre);
+        e->ckim = e->dev.up(c.kim);
+        e->crot = e->dev.up(c.rot);
     }
     return CodecTabs{e->ckre, e->ckim, e->crot, M, n, e->logN - 1};
 }
@@ -1690,8 +1468,9 @@ extern "C" int aesfhe_encode_device(aesfhe_engine* e, const double* re, const do
     hipLaunchKernelGGL(k_sfft_bitrev, dim3(blocks_for(tot)), dim3(256), 0, e->stream, (const double*)ar, (const double*)ai, br, bi, n, T.logn, B);
     const unsigned nb = blocks_for(tot);
     if (e->cflags_n < nb) {
-        if (e->cflags) HIPC(hipFree(e->cflags));
-        HIPC(hipMalloc(&e->cflags, nb * sizeof(int)));
+        e->dev.drop(e->cflags);
+        e->cflags_n = 0;
+        e->cflags = (int*)e->dev.get(nb * sizeof(int));
         e->cflags_n = nb;
     }
     hipLaunchKernelGGL(k_sfft_round, dim3(nb), dim3(256), 0, e->stream, (const double*)br, (const double*)bi, n, B, scale, co, e->cflags);
@@ -2218,26 +1997,12 @@ static BconvArgs modup_args(const aesfhe_engine* e, const u64* dc, int l, int j,
     return a;
 }
 
-// The tables of a ModDown by D = P q_l ... q_{l-r+1}: plain (r = 0) or combined with r rescales
-// (cell (r - 1, l) of the mdr_* tables, build_tables).
-struct MdTabs {
-    const double *invf, *ninvf, *einv;  // per source j: (D/e_j)^{-1} / e_j, the same times N^{-1}, 1 / e_j
-    const int8_t* tab;                  // matrix-core rows and corrections per target (bconv_mfma.h)
-    const double* corr;
-    const u64* dinv;                    // D^{-1} mod q_i per target, and as w / q for the finish
-    const double* dinvf;
-    const TwD* hatf;                    // k_moddown: (D/e_j) mod q_i, row stride hs; D mod q_i as w / q
-    int hs;
-    const double* dmodf;
-};
 static MdTabs md_tabs(const aesfhe_engine* e, int l, int r) {
     if (r < 0 || r > kMdrMaxR || e->K + r > kMdrMaxE || l - r < 0) throw_err(AESFHE_EARG, "bad combined rescale depth %d", r);
-    if (!r)
-        return {e->md_phatinvf, e->md_ninvf, e->md_einv, e->bc_md_tab, e->bc_md_corr, e->md_pinv, e->md_pinvf,
-                e->md_phatf, e->K, e->pmodf};
-    const size_t cell = (size_t)(r - 1) * e->Lp1 + l, ce = cell * kMdrMaxE, cl = cell * e->Lp1;
-    return {e->mdr_invf + ce, e->mdr_ninvf + ce, e->mdr_einv + ce, e->bc_mdr_tab + cl * 8 * kBconvKT, e->bc_mdr_corr + cl,
-            e->mdr_dinv + cl, e->mdr_dinvf + cl, e->mdr_hatf + ce * e->Lp1, kMdrMaxE, e->mdr_dmodf + cl};
+    const size_t cell = md_cell(e->Lp1, r, l), ce = cell * kMdrMaxE, cl = cell * e->Lp1;
+    const MdTabs& b = e->md;
+    return {b.invf + ce, b.ninvf + ce, b.einv + ce, b.tab + cl * kBconvRow, b.corr + cl,
+            b.dinv + cl, b.dinvf + cl, b.hatf + cl * kMdrMaxE, b.dmodf + cl};
 }
 
 // ModDown of acc's dropped limbs (the top r Q limbs + P of both components; limb t at acc + t N,
@@ -2485,14 +2250,14 @@ static void moddown_conv(aesfhe_engine* e, const MdTabs& t, u64* acc, long abs_,
             launch_bconv(e, moddown_args(e, t, acc, abs_, acs, l, r, conv, false), B * 2, K + r + 1, true);
         else  // v has no slot left on the matrix cores: the exact-fp64 VALU kernel
             AESFHE_DISPATCH16(K + r, launch_moddown, dim3(N / 512, bconv_groups(N, B * 2, lk + 1), B * 2), e->stream, (const u64*)acc, abs_, acs, l, r, conv, 2 * kN, kN,
-                              t.invf, t.hatf, t.einv, t.dmodf, e->Lp1, e->q, e->qinv, e->logN, t.hs);
+                              t.invf, t.hatf, t.einv, t.dmodf, e->Lp1, e->q, e->qinv, e->logN, kMdrMaxE);
     }
     HIPC(hipGetLastError());
 }
 
 // ModDown's conversion fused with conv's forward column pass (N = 2^16; bconv_cols.h VC): the
-// inverse column pass of the dropped limbs scales them by N^{-1} (D/e_j)^{-1} (md_ninvf /
-// mdr_ninvf), so they leave as y_j, and k_bconv_cols writes conv's column-pass intermediate
+// inverse column pass of the dropped limbs scales them by N^{-1} (D/e_j)^{-1} (MdTabs::ninvf),
+// so they leave as y_j, and k_bconv_cols writes conv's column-pass intermediate
 // straight into conv2 ([B][2][lk + 1][N], what the finishing row launch reads) -- conv's
 // coefficient form never reaches HBM.  Same residues as moddown_conv + ntt_fwd_cols.
 static bool moddown_cols_ok(const aesfhe_engine* e, int r) { return fused_bconv(e) && e->K + r + 1 <= 16; }

@@ -125,7 +125,7 @@ extern "C" int aesfhe_expand(aesfhe_engine* e, const aesfhe_ct* c, int32_t first
     Tmp mono(e, (size_t)n * ps);
     {
         ProfScope pr(e, FAM_EW, 16.0 * n * ps, "expand_mono");
-        hipLaunchKernelGGL(k_expand_mono, dim3(N / 256, nl, n), dim3(256), 0, e->stream, mono.p, (const u64*)e->ipsi, (const u64*)e->q, first, nl, e->logN);
+        hipLaunchKernelGGL(k_expand_mono, dim3(N / 256, nl, n), dim3(256), 0, e->stream, mono.p, e->tabs().ipsi, (const u64*)e->q, first, nl, e->logN);
     }
     HIPC(hipGetLastError());
     // pre-scale by (2^n)^-1: one pass over the input elements

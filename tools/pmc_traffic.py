@@ -122,7 +122,7 @@ def main():
     from bench import csrc_sha16
     out = {"head": a.head, "csrc_sha16": csrc_sha16(),
            "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE" + (" / --pmc SQ_INSTS_VALU_*_F64" if f64_counted else "")
-                     + " (separate passes, --kernel-trace) over one bench round step between marker kernels; "
+                     + " (separate passes, no tracing beside them) over one bench round step between marker kernels; "
                        "FETCH_SIZE x 2 (gfx950), tools/pmc_traffic.py",
            "ntt_family": {"classes": sorted(c for c in per if c in NTT_FAMILY), "launches": nl,
                           "hbm_bytes_per_launch": sum(p["hbm_bytes_per_launch"] * p["launches"] for p in fam) / max(nl, 1)},
