@@ -154,9 +154,10 @@ SIGNATURES = [
 SYMBOLS = [s[0] for s in SIGNATURES]
 
 # include/aesfhe_ext.h: product-only entry points (batched device plaintexts, the coefficient
-# expansion).  Bound when the library exports all of them (Lib.has_ext); the CPU oracle does not,
-# and the facade then runs the same operation through the calls above (Engine.multiply_plain_batch
-# element by element, Engine.expand step by step).
+# expansion, the exact integer combinations).  Bound when the library exports all of them
+# (Lib.has_ext); the CPU oracle does not, and the facade then runs the same operation through the
+# calls above (Engine.multiply_plain_batch element by element, Engine.expand step by step,
+# Engine.lincomb_int by double-and-add).
 c_ptb_p = C.c_void_p
 EXT_SIGNATURES = [
     ("aesfhe_ptb_create_device", C.c_int, [c_eng_p, C.c_void_p, C.c_int32, C.c_int32, _P(c_ptb_p)]),
@@ -164,6 +165,7 @@ EXT_SIGNATURES = [
     ("aesfhe_ptb_free", None, [c_ptb_p]),
     ("aesfhe_mul_ptb", C.c_int, [c_eng_p, c_ct_p, c_ptb_p, _P(c_ct_p)]),
     ("aesfhe_expand", C.c_int, [c_eng_p, c_ct_p, C.c_int32, C.c_int32, _P(c_key_p), _P(c_ct_p)]),
+    ("aesfhe_lincomb_int", C.c_int, [c_eng_p, _P(c_ct_p), C.c_int32, _P(C.c_int64), C.c_int32, _P(c_ct_p)]),
 ]
 EXT_SYMBOLS = [s[0] for s in EXT_SIGNATURES]
 

@@ -32,6 +32,10 @@ three refreshes (the bootstrap's output level L - 11).
 Counter mode (`AESSlicedRound.keystream_aes128` / `transcipher`): the
 public counter blocks enter as per-element plaintexts times K0 (no encrypted input state), the
 symmetric ciphertext is folded into the last round key: same schedule, same three refreshes.
+
+To numbers (`AESSlicedRound.transcipher_values`): `out_level` asks the
+schedule to end round 10 with levels to spare (a fourth refresh at L = 30), the bits are cleaned
+and 8 / 16 / 32 of them are summed into one value per slot, exactly (Engine.lincomb_int).
 """
 from __future__ import annotations
 
@@ -261,12 +265,17 @@ class AESRowRound:
     # levels (the 3-map CoeffToSlot one before rounds 6-7 at L = 30).
     CLEAN_LEVELS = 2
 
-    def needs_refresh(self, level: int, final: bool, since: int, refreshed: bool, stc: int) -> bool:
+    def needs_refresh(self, level: int, final: bool, since: int, refreshed: bool, stc: int,
+                      out_level: int = 0) -> bool:
         """Refresh before the next round?  When its depth does not fit, when a middle round would
-        leave fewer than `stc` (SlotToCoeff) levels, or after MAX_ROUNDS_* middle rounds."""
+        leave fewer than `stc` (SlotToCoeff) levels, after MAX_ROUNDS_* middle rounds, or when the
+        final round would end below `out_level` (the level tail a caller computes on, DESIGN.md
+        section 5.3)."""
         need = self.FINAL_DEPTH if final else self.ROUND_DEPTH
         limit = self.MAX_ROUNDS_AFTER_REFRESH if refreshed else self.MAX_ROUNDS_FRESH
-        return level < need or (not final and (level - need < stc or since >= limit))
+        if final:
+            return level - need < out_level
+        return level < need or level - need < stc or since >= limit
 
     def can_clean(self, level: int, since: int, refreshed: bool, stc: int) -> bool:
         """Clean before this refresh?  After MAX_ROUNDS_AFTER_REFRESH middle rounds from a refresh,
@@ -274,47 +283,50 @@ class AESRowRound:
         refresh only)."""
         return refreshed and since >= self.MAX_ROUNDS_AFTER_REFRESH and level - self.CLEAN_LEVELS >= stc
 
-    def refreshes_after(self, rnd: int, level: int, top: int, stc: int, with_clean: bool = False):
+    def refreshes_after(self, rnd: int, level: int, top: int, stc: int, with_clean: bool = False,
+                        out_level: int = 0):
         """Refreshes that rounds rnd..10 need when they start right after a refresh at `level`,
-        later refreshes returning `top` (inf if a round would run out of levels).  with_clean:
-        (that count, 1 if the last of those refreshes cannot be preceded by clean_bits else 0)."""
+        later refreshes returning `top` (inf if a round would run out of levels, or round 10 end
+        below `out_level`).  with_clean: (that count, 1 if the last of those refreshes cannot be
+        preceded by clean_bits else 0)."""
         n, since, lvl = 0, 0, level
         last_clean = True
         for r in range(rnd, 11):
             final = r == 10
-            if self.needs_refresh(lvl, final, since, True, stc):
+            if self.needs_refresh(lvl, final, since, True, stc, out_level):
                 if since == 0:
                     return (float("inf"), 1) if with_clean else float("inf")
                 last_clean = self.can_clean(lvl, since, True, stc)
                 n, since, lvl = n + 1, 0, top
             lvl -= self.FINAL_DEPTH if final else self.ROUND_DEPTH
             since += 1
-            if lvl < 0:
+            if lvl < (out_level if final else 0):
                 return (float("inf"), 1) if with_clean else float("inf")
         return (n, 0 if last_clean else 1) if with_clean else n
 
-    def pick_bootstrapper(self, bss, rnd: int):
+    def pick_bootstrapper(self, bss, rnd: int, out_level: int = 0):
         """The first of `bss` (cheapest first) whose output level keeps the fewest refreshes for
         rounds rnd..10: a refresh followed by two middle rounds and another refresh needs only
-        2 * 7 + StC levels, the one before the last three rounds 7 + 7 + 5."""
+        2 * 7 + StC levels, the one before the last three rounds 7 + 7 + 5 (+ out_level)."""
         if len(bss) == 1:
             return bss[0]
         stc = len(bss[0].stc_bits)
         top = max(b.bits_level for b in bss)
         # fewest refreshes first, then one that leaves room to clean before the last refresh
-        counts = [self.refreshes_after(rnd, b.bits_level, top, stc, with_clean=True) for b in bss]
+        counts = [self.refreshes_after(rnd, b.bits_level, top, stc, with_clean=True, out_level=out_level) for b in bss]
         return bss[counts.index(min(counts))]
 
     def refresh_step(self, S, rnd: int, level: int, since: int, refreshed: bool, bss, pairs_per_call: int,
-                     probe=None):
+                     probe=None, out_level: int = 0):
         """The refresh before round rnd (state S at `level`, `since` rounds after the previous
         refresh): pick the bootstrapper, clean the bits first when this is the last refresh and
         can_clean allows it, bootstrap.  Returns (state, bootstrapper, cleaned).  probe: optional
         callable(rnd, state, in_scale) shown the state the bootstrap takes (after the cleaning)."""
         stc = len(bss[0].stc_bits)
-        b = self.pick_bootstrapper(bss, rnd)
+        b = self.pick_bootstrapper(bss, rnd, out_level)
         top = max(x.bits_level for x in bss)
-        clean = self.can_clean(level, since, refreshed, stc) and self.refreshes_after(rnd, b.bits_level, top, stc) == 0
+        clean = (self.can_clean(level, since, refreshed, stc)
+                 and self.refreshes_after(rnd, b.bits_level, top, stc, out_level=out_level) == 0)
         if clean:
             S = self.clean_bits(S)
         if probe is not None:
@@ -351,44 +363,62 @@ class AESRowRound:
 
     KEY_OFFSET = 4  # a round's key product takes the SubBytes output: input level - 4
 
-    def schedule(self, L: int, bss):
+    def schedule(self, L: int, bss, out_level: int = 0):
         """[(round, input level, bootstrapper refreshing before it or None)] that encrypt_aes128
         runs from a fresh encryption at level L (ARK0 -> L - 1); bss as there (objects with
-        bits_level / stc_bits suffice)."""
+        bits_level / stc_bits suffice).  out_level: the level round 10 must end at or above (0:
+        the schedule that lands on level 0).  A positive out_level that the bootstrappers cannot
+        satisfy -- a round whose depth does not fit, a refresh without its SlotToCoeff levels, an
+        end below out_level -- is a ValueError."""
         bss = list(bss) if isinstance(bss, (list, tuple)) else [bss]
+        return self._plan(L - 1, bss, out_level)
+
+    def _plan(self, lvl: int, bss, out_level: int = 0):
+        """schedule from the state AddRoundKey(k_0) leaves at level `lvl` (bss a list)."""
         stc = len(bss[0].stc_bits)
-        out, lvl, since, nref = [], L - 1, 0, 0
+        out, since, nref = [], 0, 0
         for rnd in range(1, 11):
             final = rnd == 10
+            need = self.FINAL_DEPTH if final else self.ROUND_DEPTH
             b = None
-            if self.needs_refresh(lvl, final, since, nref > 0, stc):
-                b = self.pick_bootstrapper(bss, rnd)
+            if self.needs_refresh(lvl, final, since, nref > 0, stc, out_level):
+                b = self.pick_bootstrapper(bss, rnd, out_level)
+                if out_level and lvl < stc:
+                    raise ValueError(f"out_level {out_level}: the refresh before round {rnd} would start at level "
+                                     f"{lvl}, below SlotToCoeff's {stc}")
                 lvl, since, nref = b.bits_level, 0, nref + 1
+            if out_level and lvl - need < (out_level if final else 0):
+                raise ValueError(f"out_level {out_level}: round {rnd} from level {lvl} ends below "
+                                 f"{out_level if final else 0} (the bootstrappers return level "
+                                 f"{max(x.bits_level for x in bss)} at most)")
             out.append((rnd, lvl, b))
-            lvl -= self.FINAL_DEPTH if final else self.ROUND_DEPTH
+            lvl -= need
             since += 1
         return out
 
-    def fresh_level(self, L: int, bss) -> int:
+    def fresh_level(self, L: int, bss, out_level: int = 0) -> int:
         """The lowest level a fresh state can be encrypted at (chain top L) whose schedule needs
         no more refreshes than one from L: the first segment's spare levels (at L = 30 it reaches
         its refresh at level 8 where StC needs 3) then go unspent, and its three rounds run on
         fewer limbs -- 25 at L = 30 and at L = 35."""
         def refreshes(s):
-            return sum(b is not None for _, _, b in self.schedule(s, bss))
-        n, s = refreshes(L), L
+            try:
+                return sum(b is not None for _, _, b in self.schedule(s, bss, out_level))
+            except ValueError:  # a tail that level s cannot reach
+                return float("inf")
+        n, s = sum(b is not None for _, _, b in self.schedule(L, bss, out_level)), L
         while s > 1 and refreshes(s - 1) == n:
             s -= 1
         return s
 
-    def key_levels(self, L: int, bss) -> List[int]:
+    def key_levels(self, L: int, bss, out_level: int = 0) -> List[int]:
         """The level each of the 11 round keys is consumed at (key 0: ARK0 at L; key i: round i's
         SubBytes output level): keys encrypted there need no level-down and hold only the limbs
         they use."""
-        return [L] + [lvl - self.KEY_OFFSET for _, lvl, _ in self.schedule(L, bss)]
+        return [L] + [lvl - self.KEY_OFFSET for _, lvl, _ in self.schedule(L, bss, out_level)]
 
     def encrypt_aes128(self, bits, keys, bs, timings: dict | None = None, pairs_per_call: int = 8,
-                       progress=None, consume: bool = False, probe=None):
+                       progress=None, consume: bool = False, probe=None, out_level: int = 0):
         """AES-128 encryption of the bit state under the 11 encrypted round keys `keys`
         (FIPS-197 section 5.1), bootstrapping with `bs` (a bootstrap.Bootstrapper, or a list of them
         cheapest first: each refresh takes the first whose output level costs no extra refresh,
@@ -397,31 +427,36 @@ class AESRowRound:
         after each step.  consume: empty the rows of `bits` after AddRoundKey(k_0), so that the
         input state (the largest one, at the top level) is freed if the caller holds it only
         through that list.  probe: optional callable(rnd, state, in_scale) shown every refresh's
-        input (refresh_step)."""
+        input (refresh_step).  out_level: the level the result must keep (schedule; ValueError
+        before any ciphertext work if the bootstrappers cannot leave it)."""
         bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
+        if out_level:
+            self._plan(min(min(c.level for row in bits for c in row), keys[0][0][0].level) - 1, bss, out_level)
         S = self.add_round_key(bits, keys[0])
         if consume:
             self.e.materialize(S)
             for row in bits:
                 row.clear()
-        return self.rounds_1_to_10(S, keys, bss, timings, pairs_per_call, progress, probe)
+        return self.rounds_1_to_10(S, keys, bss, timings, pairs_per_call, progress, probe, out_level)
 
     def rounds_1_to_10(self, S, keys, bss, timings: dict | None = None, pairs_per_call: int = 8,
-                       progress=None, probe=None):
+                       progress=None, probe=None, out_level: int = 0):
         """Rounds 1..10 with their refreshes on the state S = AddRoundKey(k_0) output, under
         keys[1..10]: what encrypt_aes128 and AESSlicedRound.keystream_aes128 share (arguments as
         there, bss a list).  Returns the state and the number of refreshes."""
         import time
         stc = len(bss[0].stc_bits)
         assert all(len(b.stc_bits) == stc for b in bss)
+        if out_level:
+            self._plan(min(c.level for row in S for c in row), bss, out_level)
         refreshes = 0
         since = 0
         for rnd in range(1, 11):
             final = rnd == 10
             lvl = min(c.level for row in S for c in row)
-            if self.needs_refresh(lvl, final, since, refreshes > 0, stc):
+            if self.needs_refresh(lvl, final, since, refreshes > 0, stc, out_level):
                 t0 = time.perf_counter()
-                S, b, clean = self.refresh_step(S, rnd, lvl, since, refreshes > 0, bss, pairs_per_call, probe)
+                S, b, clean = self.refresh_step(S, rnd, lvl, since, refreshes > 0, bss, pairs_per_call, probe, out_level)
                 since = 0
                 refreshes += 1
                 if progress:
@@ -615,13 +650,9 @@ class AESSlicedRound(AESRowRound):
         return self.e.create_expansion_keys(self.sk, 0, 11)
 
     def _times(self, ct: Ciphertext, m: int) -> Ciphertext:
-        """ct times the positive integer m, exactly and without a level: double and add."""
-        acc = ct
-        for bit in bin(m)[3:]:
-            acc = self.e.add(acc, acc)
-            if bit == "1":
-                acc = self.e.add(acc, ct)
-        return acc
+        """ct times the integer m, exactly and without a level (Engine.lincomb_int: one launch on
+        the HIP engine, double and add on the oracle)."""
+        return self.e.lincomb_int([ct], [[m]])[0]
 
     def expand_key_subtree(self, el: Ciphertext, xkeys, level: int, bundle_level: int) -> Ciphertext:
         """One key's element of the first stage (batch 1, its bits at bundle_amplitude) -> the 128
@@ -790,14 +821,14 @@ class AESSlicedRound(AESRowRound):
         keystream XOR data without a level of the state."""
         return self.mul_planes(key, self.data_planes(data))
 
-    def ctr_key_levels(self, L: int, bss) -> List[int]:
+    def ctr_key_levels(self, L: int, bss, out_level: int = 0) -> List[int]:
         """key_levels for keystream_aes128 with `data`: the last key one level higher, the level
         fold_data_key spends."""
-        lv = self.key_levels(L, bss)
+        lv = self.key_levels(L, bss, out_level)
         return lv[:-1] + [lv[-1] + 1]
 
     def keystream_aes128(self, iv, nb: int, keys, bs, first: int = 0, data=None, timings: dict | None = None,
-                         pairs_per_call: int = 8, progress=None, probe=None):
+                         pairs_per_call: int = 8, progress=None, probe=None, out_level: int = 0):
         """AES-128 of the counter blocks first, first + 1, ... of `iv` (aes_tables.ctr_blocks) for
         `nb` sets of n_blk blocks under the encrypted round keys: the CTR keystream as +-1 bit
         ciphertexts, with no encrypted input state.  State 0 is counter_state(keys[0], ...) --
@@ -805,22 +836,148 @@ class AESSlicedRound(AESRowRound):
         in encrypt_aes128 (rounds_1_to_10).  With `data` ((nb, n_blk, 16) bytes) the result is
         keystream XOR data (fold_data_key into keys[10], which must then sit one level above the
         one round 10 consumes: ctr_key_levels).  `first` lets a rank derive the counters of its
-        own slab range.  Returns the state and the number of refreshes."""
+        own slab range.  out_level: the level the result must keep (schedule; the keys then sit at
+        key_levels / ctr_key_levels of the same out_level).  Returns the state and the number of
+        refreshes."""
         bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
         keys = list(keys)
+        if out_level:
+            self.schedule(keys[0][0][0].level, bss, out_level)  # ValueError before any ciphertext work
         if data is not None:
             if tuple(data.shape) != (nb, self.n_blk, 16):
                 raise ValueError(f"data must be ({nb}, {self.n_blk}, 16) bytes, got {tuple(data.shape)}")
-            want = self.ctr_key_levels(keys[0][0][0].level, bss)[10]
+            want = self.ctr_key_levels(keys[0][0][0].level, bss, out_level)[10]
             if keys[10][0][0].level < want:
                 raise ValueError(f"keys[10] is at level {keys[10][0][0].level}; folding data into it needs "
                                  f"level {want} (ctr_key_levels)")
             keys[10] = self.fold_data_key(keys[10], data)
         S = self.counter_state(keys[0], iv, nb, first)
-        return self.rounds_1_to_10(S, keys, bss, timings, pairs_per_call, progress, probe)
+        return self.rounds_1_to_10(S, keys, bss, timings, pairs_per_call, progress, probe, out_level)
 
-    def transcipher(self, data, iv, keys, bs, first: int = 0, **kw):
+    def transcipher(self, data, iv, keys, bs, first: int = 0, out_level: int = 0, **kw):
         """AES-128-CTR decryption of `data` ((NB, n_blk, 16) bytes encrypted from counter `first`
         of `iv`) under the encrypted round keys: the +-1 bit ciphertexts of the message
-        (decrypt_blocks reads them), and the number of refreshes."""
-        return self.keystream_aes128(iv, data.shape[0], keys, bs, first=first, data=data, **kw)
+        (decrypt_blocks reads them), and the number of refreshes.  out_level: the level those
+        ciphertexts keep (keystream_aes128)."""
+        return self.keystream_aes128(iv, data.shape[0], keys, bs, first=first, data=data, out_level=out_level, **kw)
+
+    # ---- bits to values (DESIGN.md section 5.3) ------------------------------------------------
+    VALUE_WIDTHS = (8, 16, 32)
+
+    def _value_groups(self, width: int, byteorder: str):
+        """The output groups of a value width: per group the (row, shift) of every byte a value
+        spans, shift = the weight 2^shift of that byte's bit 0.  Group g covers the rows
+        g * width / 8 .. (g + 1) * width / 8 - 1; row r of a column is byte 4c + r of the block, so
+        'big' gives the lowest row the highest shift."""
+        if width not in self.VALUE_WIDTHS:
+            raise ValueError(f"width must be one of {self.VALUE_WIDTHS}, got {width}")
+        if byteorder not in ("big", "little"):
+            raise ValueError("byteorder must be 'big' or 'little'")
+        nby = width // 8
+        return [[(g * nby + i, 8 * (nby - 1 - i if byteorder == "big" else i)) for i in range(nby)]
+                for g in range(4 // nby)]
+
+    def values_from_bits(self, bits, width: int, byteorder: str = "big", in_scale: float = 1.0):
+        """The +-1 bit state -> ciphertexts of `width`-bit unsigned values, width in {8, 16, 32}:
+        (cts, amplitude).  Bit p of a value is bits[r][p mod 8] (bit j of a byte has weight 2^j, as
+        in counter_planes / decrypt_blocks), r the row holding that byte of the value: a value
+        never leaves its column, whose rows 0..3 are the bytes 4c .. 4c + 3 of the block.
+          width 8:  4 outputs, output g = row g                (value 4c + g of the block)
+          width 16: 2 outputs, output g = rows 2g, 2g + 1      (value 2c + g)
+          width 32: 1 output,  rows 0..3                       (value c)
+        the first byte the most significant with byteorder 'big'.  Every output keeps the sliced
+        batch: element 4 s + c, slot k holds the value taken from column c of block k of slab s
+        (pack's order: block k of slab s is block number s * slot_count + k of the message, sets
+        in order, n_blk blocks each; decode_values undoes the map).  One Engine.lincomb_int per output with the weights -2^p:
+        a bit ciphertext holds in_scale * (1 - 2 bit), so the slot is
+        amplitude * (2 v - (2^width - 1)), the centred value -- an odd integer times
+        amplitude = in_scale.  Exact and level-free: the only error is the bits' own deviation,
+        at most (2^width - 1) * bit_margin in units of amplitude.  ValueError when the largest
+        coefficient, 2 * amplitude * 2^width * Delta_level, does not fit under Q_level / 2."""
+        groups = self._value_groups(width, byteorder)
+        amplitude = float(in_scale)
+        level = bits[0][0].level
+        Q = 1
+        for q in self.e.primes[:level + 1]:
+            Q *= int(q)
+        if 2.0 * amplitude * 2.0 ** width * self.e.scales[level] >= Q / 2:
+            raise ValueError(f"{width}-bit values at amplitude {amplitude} need 2^{width + 1} * amplitude * Delta "
+                             f"below Q / 2 = 2^{Q.bit_length() - 2}: level {level} is too low, keep a level more")
+        cts = []
+        for grp in groups:
+            ins = [bits[r][j] for r, _ in grp for j in range(8)]
+            cts.append(self.e.lincomb_int(ins, [[-(1 << (sh + j)) for _, sh in grp for j in range(8)]])[0])
+        return cts, amplitude
+
+    def value_slots(self, ct: Ciphertext, width: int, amplitude: float) -> np.ndarray:
+        """The slots (batch, slot_count) of one values_from_bits output, decrypted (client side):
+        amplitude * (2 v - (2^width - 1)) plus the error.  aesfhe_decrypt hands coefficients
+        back as int64, which amplitude * 2^(width + 1) * Delta overflows for 32-bit values at a
+        40-bit scale: such a ciphertext is first multiplied by an integer C (exactly,
+        Engine.lincomb_int) and rescaled, so that it decrypts at the scale Delta C / q_level with
+        coefficients below 2^61, and the slots are scaled back.  That takes a level of the
+        client's copy (ValueError at level 0, or when Q_level has no room for any C >= 1)."""
+        e = self.e
+        lvl = ct.level
+        D = e.scales[lvl]
+        peak = float(amplitude) * 2.0 ** (width + 1) * D  # bounds every slot, hence every coefficient
+        if peak < 2.0 ** 62:
+            return np.real(np.atleast_2d(e.decrypt(ct, self.sk)))
+        Q = 1
+        for q in e.primes[:lvl + 1]:
+            Q *= int(q)
+        ql = int(e.primes[lvl])
+        C = min(int(2.0 ** 61 * ql / peak), Q // (2 * int(peak) + 2)) if lvl >= 1 else 0
+        if C < 1:
+            raise ValueError(f"{width}-bit values at level {lvl} cannot be brought under the int64 coefficients of "
+                             f"a decryption: keep a level more")
+        y = e.rescale(e.lincomb_int([ct], [[C]])[0])
+        return np.real(np.atleast_2d(e.decrypt(y, self.sk))) * (e.scales[lvl - 1] * ql / (D * C))
+
+    def decode_values(self, cts, nb: int, width: int, amplitude: float) -> np.ndarray:
+        """values_from_bits' outputs, decrypted (client side): the values v as float64 in message
+        order, shape (nb, n_blk, 128 // width) -- value i of a block is its bytes
+        i * width / 8 .. (i + 1) * width / 8 - 1.  Not rounded: v = (slot / amplitude +
+        2^width - 1) / 2."""
+        G = len(cts)
+        if width not in self.VALUE_WIDTHS or G != 32 // width:
+            raise ValueError(f"width {width} has {32 // width if width in self.VALUE_WIDTHS else '?'} outputs, got {G}")
+        S = cts[0].batch // 4
+        out = np.empty((S, self.sc, 4 * G), dtype=np.float64)
+        for g, ct in enumerate(cts):
+            x = self.value_slots(ct, width, amplitude).reshape(S, 4, self.sc)
+            for c in range(4):
+                out[:, :, c * G + g] = (x[:, c, :] / amplitude + (2.0 ** width - 1.0)) / 2.0
+        return out.reshape(-1, 4 * G)[:int(nb) * self.n_blk].reshape(int(nb), self.n_blk, 4 * G)
+
+    def transcipher_values(self, data, iv, keys, bs, width: int, byteorder: str = "big", first: int = 0,
+                           clean: bool = True, keep_levels: int = 0, **kw):
+        """transcipher, then the message as `width`-bit values: (cts, amplitude, refreshes), cts
+        and amplitude as values_from_bits gives them, at level keep_levels or above (what
+        schedule(L, bs, t) leaves after round 10, less the cleaning).  The schedule keeps a tail
+        of t = (CLEAN_LEVELS if clean else 0) + keep_levels levels (transcipher's out_level);
+        with `clean` the bits are cleaned first (clean_bits: deviation e -> ~1.5 e^2, amplitude
+        2).  The keys must sit at ctr_key_levels(L, bs, out_level=t), L = keys[0]'s level.  A
+        width whose values do not fit level keep_levels (values_from_bits) and keys at other
+        levels are ValueErrors before any ciphertext work."""
+        bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
+        self._value_groups(width, byteorder)
+        t = (self.CLEAN_LEVELS if clean else 0) + int(keep_levels)
+        L = keys[0][0][0].level
+        want = self.ctr_key_levels(L, bss, out_level=t)  # ValueError if no bootstrapper leaves t levels
+        have = [k[0][0].level for k in keys]
+        if have != want:
+            raise ValueError(f"keys at levels {have}; a tail of {t} levels needs {want} "
+                             f"(ctr_key_levels(L, bs, out_level={t}))")
+        end = self.schedule(L, bss, t)[-1][1] - self.FINAL_DEPTH - (self.CLEAN_LEVELS if clean else 0)
+        amp = 2.0 if clean else 1.0
+        Q = 1
+        for q in self.e.primes[:end + 1]:
+            Q *= int(q)
+        if 2.0 * amp * 2.0 ** width * self.e.scales[end] >= Q / 2:
+            raise ValueError(f"{width}-bit values do not fit level {end}: raise keep_levels")
+        bits, refreshes = self.transcipher(data, iv, keys, bss, first=first, out_level=t, **kw)
+        if clean:
+            bits = self.clean_bits(bits)
+        cts, amplitude = self.values_from_bits(bits, width, byteorder, in_scale=amp)
+        return cts, amplitude, refreshes

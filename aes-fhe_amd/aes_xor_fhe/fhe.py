@@ -905,6 +905,81 @@ class Engine:
             c = self.concat([s, self._monomial_shift(d, 1 << (first + i))])
         return c
 
+    # -- exact integer combinations ----------------------------------------------
+    LINCOMB_INT_MAX_IN, LINCOMB_INT_MAX_OUT = 32, 16
+
+    def lincomb_int(self, cts: Sequence[Ciphertext], weights) -> list:
+        """outs[r] = sum_i weights[r][i] * cts[i] for an (m, n) matrix of Python / int64 integers
+        (any but -2^63), exactly: residue by residue mod every prime of the inputs' common level,
+        no rounding and no rescale, so level and scale are the inputs' (1 <= n <= 32,
+        1 <= m <= 16; equal level, npoly and batch).  The HIP engine runs aesfhe_lincomb_int, one
+        launch; a backend without include/aesfhe_ext.h (the CPU oracle, the checker of that path)
+        composes the same sums through aesfhe.h: negate for the signs, then double-and-add over
+        the bits of the |weights| with aesfhe_add (Horner over all inputs of a row at once) --
+        slow, and identical residues because every step is exact."""
+        cts = list(cts)
+        n = len(cts)
+        W = [[int(x) for x in row] for row in weights]
+        m = len(W)
+        if any(len(row) != n for row in W):
+            raise ValueError(f"lincomb_int: every weight row needs {n} entries")
+        if any(not -(1 << 63) < x < (1 << 63) for row in W for x in row):
+            raise ValueError("lincomb_int: weights must fit an int64 (and not be -2^63)")
+        if self._lib.has_ext:
+            arr = (c_ct_p * max(n, 1))(*[c._h for c in cts])
+            wa = np.ascontiguousarray(np.array(W, dtype=np.int64).reshape(-1))
+            if wa.size == 0:
+                wa = np.zeros(1, dtype=np.int64)
+            outs = (c_ct_p * max(m, 1))()
+            self._check(self._lib.lincomb_int(self._h, arr, n, _as_ptr(wa, C.c_int64), m, outs))
+            return [self._ct(outs[i]) for i in range(m)]
+        if self.on_device:  # the product never takes the checker's path
+            raise RuntimeError(f"{self._lib.path}: the HIP engine lacks include/aesfhe_ext.h: rebuild it")
+        # aesfhe_lincomb_int's own refusals
+        bad = f"[{self._lib.backend}] invalid argument: "
+        if not 1 <= n <= self.LINCOMB_INT_MAX_IN:
+            raise RuntimeError(bad + f"{n} inputs not in 1..{self.LINCOMB_INT_MAX_IN}")
+        if not 1 <= m <= self.LINCOMB_INT_MAX_OUT:
+            raise RuntimeError(bad + f"{m} outputs not in 1..{self.LINCOMB_INT_MAX_OUT}")
+        c0 = cts[0]
+        for i, c in enumerate(cts):
+            if c.level != c0.level:
+                raise RuntimeError(f"[{self._lib.backend}] level error: input {i} at level {c.level}, input 0 at "
+                                   f"level {c0.level}")
+            if c.npoly != c0.npoly:
+                raise RuntimeError(f"[{self._lib.backend}] degree error: Input {i} has {c.npoly} polynomials, "
+                                   f"input 0 has {c0.npoly}")
+            if c.batch != c0.batch:
+                raise RuntimeError(bad + f"batch mismatch {c.batch} vs {c0.batch}")
+        neg = {}  # the negated inputs, made once
+
+        def signed(i, w):
+            if w > 0:
+                return cts[i]
+            if i not in neg:
+                neg[i] = self.negate(cts[i])
+            return neg[i]
+        outs = []
+        for row in W:
+            live = [(i, w) for i, w in enumerate(row) if w and not cts[i].is_zero]
+            flip = bool(live) and all(w < 0 for _, w in live)  # all negative: one negation, of the sum
+            terms = [(signed(i, -w if flip else w), abs(w)) for i, w in live]
+            acc = None
+            for b in range(max((a.bit_length() for _, a in terms), default=0) - 1, -1, -1):
+                if acc is not None:
+                    acc = self._call_ct(self._lib.add, acc._h, acc._h)
+                for c, a in terms:
+                    if (a >> b) & 1:
+                        acc = c if acc is None else self._call_ct(self._lib.add, acc._h, c._h)
+            if acc is None:  # no contribution: a zero ciphertext of the inputs' shape
+                acc = self.zeros(c0.batch, c0.level) if c0.npoly == 2 else self.subtract(c0, c0)
+            elif flip:
+                acc = self.negate(acc)
+            elif any(acc is c for c in cts):  # a lone weight 1: the result must not alias its input
+                acc = self._call_ct(self._lib.ct_copy, acc._h)
+            outs.append(acc)
+        return outs
+
     # -- deferred linear combinations (_LinearCiphertext) -------------------------------------
     def _linear_add(self, a, b):
         """a + b with at least one deferred operand: the merged deferred sum, or None when b is

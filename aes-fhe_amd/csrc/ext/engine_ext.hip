@@ -1,11 +1,12 @@
 // engine_ext.hip -- the translation unit libaesfhe.so is built from: the engine of ../engine.hip
 // (whose helpers are file-static, hence the inclusion) plus the product-only entry points of
 // include/aesfhe_ext.h: the batched device plaintexts and the
-// coefficient expansion (section 3.22).
+// coefficient expansion (section 3.22) and the exact integer combinations (section 5.3).
 #include "../engine.hip"
 
 #include "../../../include/aesfhe_ext.h"
 #include "kernels_expand.h"
+#include "kernels_lincomb_int.h"
 #include "kernels_ptb.h"
 
 struct aesfhe_ptb {
@@ -154,5 +155,81 @@ extern "C" int aesfhe_expand(aesfhe_engine* e, const aesfhe_ct* c, int32_t first
         cur = std::move(nxt);
     }
     *out = cur.release();
+    API_END
+}
+
+// -----------------------------------------------------------------------------------------------
+// exact integer combinations
+
+// w mod q with w's sign, in [0, q)
+static u64 signed_res(int64_t w, u64 q) {
+    const u64 a = (w < 0 ? (u64)0 - (u64)w : (u64)w) % q;
+    return w < 0 && a ? q - a : a;
+}
+
+template <int MT>
+static void launch_lincomb_int(aesfhe_engine* e, dim3 grid, const u64* const* in, int n, const u64* w, int m, u64* out, long orow, long ps,
+                               int nl) {
+    hipLaunchKernelGGL(k_lincomb_int<MT>, grid, dim3(256), 0, e->stream, in, n, w, m, out, orow, ps, nl, (const u64*)e->q,
+                       (const double*)e->qinv, e->logN);
+}
+
+extern "C" int aesfhe_lincomb_int(aesfhe_engine* e, const aesfhe_ct* const* cts, int32_t n, const int64_t* w, int32_t m, aesfhe_ct** outs) {
+    API_BEGIN
+    if (!e || !cts || !w || !outs) throw_err(AESFHE_EARG, "null argument");
+    if (n < 1 || n > kLincombIntMaxIn) throw_err(AESFHE_EARG, "%d inputs not in 1..%d", n, kLincombIntMaxIn);
+    if (m < 1 || m > kLincombIntMaxOut) throw_err(AESFHE_EARG, "%d outputs not in 1..%d", m, kLincombIntMaxOut);
+    for (int i = 0; i < n; i++)
+        if (!cts[i] || cts[i]->eng != e) throw_err(AESFHE_EARG, "input %d is not a ciphertext of this engine", i);
+    const int B = cts[0]->B, np = cts[0]->np, l = cts[0]->level, nl = l + 1, N = e->N;
+    for (int i = 1; i < n; i++) {
+        if (cts[i]->level != l) throw_err(AESFHE_ELEVEL, "input %d at level %d, input 0 at level %d", i, cts[i]->level, l);
+        if (cts[i]->np != np) throw_err(AESFHE_EDEGREE, "Input %d has %d polynomials, input 0 has %d", i, cts[i]->np, np);
+        if (cts[i]->B != B) throw_err(AESFHE_EARG, "batch mismatch %d vs %d", cts[i]->B, B);
+    }
+    for (long t = 0; t < (long)m * n; t++)
+        if (w[t] == INT64_MIN) throw_err(AESFHE_EARG, "weight %ld is INT64_MIN", t);
+    if (N < 512 || (long)B * np > kMaxGridZ) throw_err(AESFHE_EARG, "shape outside the kernel's grid (N %d, batch %d)", N, B);
+    // the inputs that contribute: a non-zero weight somewhere in their column, not a zero ciphertext
+    std::vector<int> cols;
+    for (int i = 0; i < n; i++) {
+        bool any = false;
+        for (int r = 0; r < m; r++) any = any || w[(size_t)r * n + i] != 0;
+        if (any && !cts[i]->is_zero) cols.push_back(i);
+    }
+    const int nc = (int)cols.size();
+    std::vector<CtPtr> res(m);
+    if (nc == 0) {
+        for (int r = 0; r < m; r++) res[r] = ct_zero_new(e, B, np, l);
+    } else {
+        std::vector<const u64*> ptr(nc);
+        std::vector<u64> W((size_t)m * nc * nl);
+        std::vector<char> live(m, 0);
+        for (int c = 0; c < nc; c++) ptr[c] = cts[cols[c]]->d;
+        for (int r = 0; r < m; r++)
+            for (int c = 0; c < nc; c++) {
+                const int64_t wv = w[(size_t)r * n + cols[c]];
+                live[r] = live[r] || wv != 0;
+                for (int k = 0; k < nl; k++) W[((size_t)r * nc + c) * nl + k] = signed_res(wv, e->chain.q[k]);
+            }
+        const long ps = (long)nl * N, orow = (long)B * np * ps;
+        CtPtr all = ct_new(e, m * B, np, l);
+        const u64* const* dptr = upload_small(e, ptr.data(), ptr.size());
+        const u64* dW = upload_small(e, W.data(), W.size());
+        {
+            ProfScope pr(e, FAM_EW, 8.0 * ps * B * np * (double)(nc + m), "lincomb_int");
+            const dim3 grid(N / 512, nl, B * np);
+            if (m == 1) launch_lincomb_int<1>(e, grid, dptr, nc, dW, m, all->d, orow, ps, nl);
+            else if (m == 2) launch_lincomb_int<2>(e, grid, dptr, nc, dW, m, all->d, orow, ps, nl);
+            else if (m <= 4) launch_lincomb_int<4>(e, grid, dptr, nc, dW, m, all->d, orow, ps, nl);
+            else if (m <= 8) launch_lincomb_int<8>(e, grid, dptr, nc, dW, m, all->d, orow, ps, nl);
+            else launch_lincomb_int<16>(e, grid, dptr, nc, dW, m, all->d, orow, ps, nl);
+        }
+        HIPC(hipGetLastError());
+        res = ct_split_batch(e, std::move(all), m);
+        // a row without a contribution was written as zeros
+        for (int r = 0; r < m; r++) res[r]->is_zero = !live[r];
+    }
+    release_all(res, outs);
     API_END
 }

@@ -16,6 +16,11 @@
  * round keys as a single ciphertext.  It needs an exact, level-free product with a monomial, which
  * aesfhe.h does not offer on the device; the oracle's facade path shifts coefficients on the host.
  *
+ * And the exact integer combinations (aesfhe_lincomb_int below): weighted sums of ciphertexts with
+ * int64 weights that spend no level, where aesfhe_lincomb rounds real weights against mul_scale and
+ * rescales -- what sums the bit ciphertexts of a transciphered message into numbers.  The oracle's
+ * facade path composes them from aesfhe_negate and aesfhe_add.
+ *
  * Only libaesfhe.so (HIP, gfx950) exports these; the oracle does not, and AESFHE_ABI_VERSION is
  * unchanged.  Conventions (error codes, handles, aesfhe_last_error) are those of aesfhe.h.
  */
@@ -67,6 +72,20 @@ int aesfhe_mul_ptb(aesfhe_engine *eng, const aesfhe_ct *ct, const aesfhe_ptb *pt
  * refused call takes no device memory and enqueues nothing. */
 int aesfhe_expand(aesfhe_engine *eng, const aesfhe_ct *ct, int32_t first_step, int32_t n_steps,
                   const aesfhe_key *const *keys, aesfhe_ct **out);
+
+/* Exact integer combinations: outs[r] = sum_i w[r * n + i] * cts[i] for
+ * r < m, residue by residue mod every q_k of the inputs' level.  Nothing is rounded and nothing
+ * rescaled: level and canonical scale are the inputs', so the plaintext is the same integer
+ * combination of the inputs' plaintexts (and of their noise).  A weight is reduced mod q_k with
+ * its sign, so |w| >= q_k is fine; any int64 but INT64_MIN (AESFHE_EARG).  1 <= n <= 32,
+ * 1 <= m <= 16, else AESFHE_EARG.  All inputs have one level (else AESFHE_ELEVEL), one npoly
+ * (AESFHE_EDEGREE) and one batch (AESFHE_EARG): there is no alignment and no broadcast.  An input
+ * whose column of w is all zero is not read; a zero ciphertext contributes nothing, and an output
+ * with no contribution is a zero ciphertext (as aesfhe_add's of two zero ciphertexts).  One kernel
+ * launch: every input word is read once for all m outputs.  A refused call takes no device
+ * memory and enqueues nothing. */
+int aesfhe_lincomb_int(aesfhe_engine *eng, const aesfhe_ct *const *cts, int32_t n,
+                       const int64_t *w /* row-major [m][n] */, int32_t m, aesfhe_ct **outs);
 
 #ifdef __cplusplus
 }
