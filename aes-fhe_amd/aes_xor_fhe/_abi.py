@@ -166,6 +166,12 @@ EXT_SIGNATURES = [
     ("aesfhe_mul_ptb", C.c_int, [c_eng_p, c_ct_p, c_ptb_p, _P(c_ct_p)]),
     ("aesfhe_expand", C.c_int, [c_eng_p, c_ct_p, C.c_int32, C.c_int32, _P(c_key_p), _P(c_ct_p)]),
     ("aesfhe_lincomb_int", C.c_int, [c_eng_p, _P(c_ct_p), C.c_int32, _P(C.c_int64), C.c_int32, _P(c_ct_p)]),
+    # the compact wire format (Engine.pack_key / pack_ciphertext / unpack; the oracle's facade path
+    # is wire.py over the export / import calls above)
+    ("aesfhe_key_pack", C.c_int, [c_eng_p, c_key_p, c_key_p, C.c_char_p, C.c_void_p, _P(C.c_int64)]),
+    ("aesfhe_key_unpack", C.c_int, [c_eng_p, C.c_char_p, C.c_int64, _P(c_key_p)]),
+    ("aesfhe_ct_pack", C.c_int, [c_eng_p, c_ct_p, c_key_p, C.c_char_p, C.c_void_p, _P(C.c_int64)]),
+    ("aesfhe_ct_unpack", C.c_int, [c_eng_p, C.c_char_p, C.c_int64, _P(c_ct_p)]),
 ]
 EXT_SYMBOLS = [s[0] for s in EXT_SIGNATURES]
 

@@ -23,6 +23,7 @@ from typing import Sequence
 
 import numpy as np
 
+from . import wire
 from ._abi import Lib, Params, c_ct_p, c_key_p, c_pt_p, load_product
 
 # HomomorphicEncryption.org 128-bit bound on log2(QP) for ternary secrets
@@ -1398,12 +1399,106 @@ class Engine:
             fp["digit_primes"] = self.digit_primes
         return fp
 
-    def save(self, obj, path) -> None:
+    # -- compact wire format ---------------------------------------------------
+    def _pack(self, fn, fallback, obj, sk, seed) -> bytes:
+        if sk is None and seed is not None:
+            raise ValueError("a seed without the secret key: seeded packing re-masks with sk (pass sk, or no seed)")
+        if sk is not None:
+            seed = os.urandom(32) if seed is None else bytes(seed)
+            if len(seed) != 32:
+                raise ValueError("the seed is 32 bytes")
+        if not self._lib.has_ext:
+            return fallback(self, obj, sk, seed)
+        skh = getattr(sk, "_h", None) if sk is not None else None
+        if sk is not None and (skh is None or getattr(sk, "engine", None) is not self):
+            raise wire.WireError(-1, self._lib.backend, "seeded packing needs a secret key of this engine")
+        need = C.c_int64()
+        self._check(fn(self._h, obj._h, skh, seed if sk is not None else None, None, C.byref(need)))
+        buf = bytearray(need.value)
+        self._check(fn(self._h, obj._h, skh, seed if sk is not None else None,
+                       C.addressof((C.c_char * len(buf)).from_buffer(buf)), C.byref(need)))
+        return bytes(buf)
+
+    def pack_key(self, key, sk=None, seed: bytes | None = None) -> bytes:
+        """A key as a compact blob: every residue packed to the bit length of its prime.  With
+        `sk` -- the secret key the key's rows are encrypted under: the secret key itself for
+        public, relinearisation, galois and hoisted keys, sk_to for a create_switching_key key --
+        the blob is seeded: the mask half of every (b, a) pair is replaced by one expanded from
+        the 32 public bytes `seed` (os.urandom by default) and left out, b re-masked so that
+        b + a s is unchanged residue for residue.  One seed must not serve two keys of equal
+        (kind, galois element), e.g. two switching keys made by create_switching_key: equal masks
+        would reveal the difference of what they encrypt (save_evaluation_keys derives a seed
+        per key)."""
+        return self._pack(getattr(self._lib, "key_pack", None), wire.pack_key, key, sk, seed)
+
+    def pack_ciphertext(self, ct: Ciphertext, sk=None, seed: bytes | None = None) -> bytes:
+        """A ciphertext as a compact blob; with `sk` (the secret key; 2 polynomials only) c1 is
+        replaced by a mask expanded from `seed` and left out, as pack_key.  One seed per
+        ciphertext."""
+        return self._pack(getattr(self._lib, "ct_pack", None), wire.pack_ciphertext, ct, sk, seed)
+
+    def _key_class(self, kind: int, g: int):
+        """The key class of an unpacked key from its kind and galois element."""
+        if kind == 3 and g == 4 * self.slot_count - 1:
+            return ConjugationKey
+        if kind in (0, 1, 2):
+            return (SecretKey, PublicKey, RelinearizationKey)[kind]
+        # a rotation's element is a power of 5 other than 1 (1: a switching key)
+        return FixedRotationKey if g % 4 == 1 and g != 1 else GaloisKey
+
+    def _rotation_of(self, g: int):
+        """The np.roll step r of a rotation's galois element, g = 5^((n - r) mod n) mod 2N
+        (aesfhe_galois_elt); None if g is no power of 5.  At most n steps."""
+        n, p = self.slot_count, 1
+        for x in range(n):
+            if p == g:
+                return (n - x) % n
+            p = p * 5 % (4 * n)
+        return None
+
+    def unpack(self, blob, cls=None, delta: int | None = None):
+        """The Ciphertext or key of a blob made by pack_key / pack_ciphertext on an engine with
+        this one's parameters (anything else raises).  `cls`: the key class to return; by default
+        it follows the kind and the galois element (a rotation's element gives a
+        FixedRotationKey).  `delta`: a FixedRotationKey's rotation when the caller knows it;
+        otherwise it is recovered from the galois element (up to N / 2 steps of a Python loop)."""
+        blob = bytes(blob)
+        is_key = len(blob) >= 16 and int.from_bytes(blob[12:16], "little") == wire.TYPE_KEY
+        if self._lib.has_ext:
+            out = C.c_void_p()
+            fn = self._lib.key_unpack if is_key else self._lib.ct_unpack
+            self._check(fn(self._h, blob, len(blob), C.byref(out)))
+            h = out.value
+        else:
+            h = wire.import_rows(self, *wire.unpack_rows(self, blob))
+        if not is_key:
+            return self._ct(h)
+        kind, g = C.c_int32(), C.c_uint64()
+        self._lib.key_info(h, C.byref(kind), C.byref(g))
+        k = self._key(cls or self._key_class(kind.value, g.value), h)
+        if isinstance(k, GaloisKey):
+            k.galois_elt = g.value
+        if isinstance(k, FixedRotationKey):
+            k.delta = int(delta) if delta is not None else self._rotation_of(g.value)
+        return k
+
+    def save(self, obj, path, compact: bool = False, sk=None, seed: bytes | None = None) -> None:
         """Write a Ciphertext or key (SecretKey, PublicKey, RelinearizationKey, GaloisKey and
         subclasses) to `path`: magic, a JSON header (kind, shape, the engine's prime chain) and
         the NTT-domain residues as little-endian u64.  A RotationKey is not saved: it is derived
-        on use from its secret key."""
+        on use from its secret key.  compact: the file is the blob of pack_key / pack_ciphertext
+        (seeded under `seed` when `sk` is given) instead; load reads either."""
         import json
+        if compact:
+            if isinstance(obj, Ciphertext):
+                blob = self.pack_ciphertext(obj, sk, seed)
+            elif isinstance(obj, _Key):
+                blob = self.pack_key(obj, sk, seed)
+            else:
+                raise TypeError(f"cannot save {type(obj).__name__}")
+            with open(path, "wb") as f:
+                f.write(blob)
+            return
         hdr = {"fp": self._fingerprint()}
         if isinstance(obj, Ciphertext):
             data = self.export_residues(obj)
@@ -1429,7 +1524,10 @@ class Engine:
         other parameters (prime chain)."""
         import json
         with open(path, "rb") as f:
-            if f.read(len(_MAGIC)) != _MAGIC:
+            magic = f.read(len(_MAGIC))
+            if magic == wire.MAGIC:  # a compact blob (save(compact=True))
+                return self.unpack(magic + f.read())
+            if magic != _MAGIC:
                 raise RuntimeError(f"{path}: not an aes-fhe object file")
             hdr = json.loads(f.read(int.from_bytes(f.read(8), "little")))
             data = np.frombuffer(f.read(), dtype="<u8")

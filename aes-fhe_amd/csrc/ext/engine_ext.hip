@@ -1,13 +1,15 @@
 // engine_ext.hip -- the translation unit libaesfhe.so is built from: the engine of ../engine.hip
 // (whose helpers are file-static, hence the inclusion) plus the product-only entry points of
 // include/aesfhe_ext.h: the batched device plaintexts and the
-// coefficient expansion (section 3.22) and the exact integer combinations (section 5.3).
+// coefficient expansion (section 3.22), the exact integer combinations (section 5.3) and the
+// compact wire format (section 3.23).
 #include "../engine.hip"
 
 #include "../../../include/aesfhe_ext.h"
 #include "kernels_expand.h"
 #include "kernels_lincomb_int.h"
 #include "kernels_ptb.h"
+#include "kernels_wire.h"
 
 struct aesfhe_ptb {
     aesfhe_engine* eng;
@@ -231,5 +233,170 @@ extern "C" int aesfhe_lincomb_int(aesfhe_engine* e, const aesfhe_ct* const* cts,
         for (int r = 0; r < m; r++) res[r]->is_zero = !live[r];
     }
     release_all(res, outs);
+    API_END
+}
+
+// -----------------------------------------------------------------------------------------------
+// compact wire format (wire_format.h sizes and validates everything)
+
+static WireDims wire_dims(const aesfhe_engine* e) {
+    WireDims d;
+    d.logN = e->logN, d.L = e->L, d.K = e->K, d.dnum = e->dnum;
+    d.q = e->chain.q.data();
+    d.digest = wire_digest(e->logN, e->L, e->K, e->A, d.q);
+    return d;
+}
+
+static WireHeader wire_header_of(const aesfhe_engine* e, const WireDims& d) {
+    WireHeader h;
+    h.logN = d.logN, h.L = d.L, h.K = d.K, h.digest = d.digest;
+    return h;
+}
+
+// Header and shape of an object about to be packed; the size protocol of dst / *bytes.  Returns
+// false when the call is complete without a launch (size query).
+static bool wire_pack_begin(const aesfhe_engine* e, const WireDims& d, WireHeader& h, WireShape& s, const uint8_t* seed, bool seeded,
+                            const void* dst, int64_t* bytes) {
+    if (e->logN < kWireMinLogN) throw_err(AESFHE_EARG, "the wire format needs N >= 1024");
+    h.seeded = seeded;
+    if (seeded) memcpy(h.seed, seed, 32);
+    const std::string err = wire_shape(h, d, s);
+    if (!err.empty()) throw_err(AESFHE_EARG, "cannot pack: %s", err.c_str());
+    h.payload = wire_payload_bytes(s, d.q, d.logN);
+    const int64_t total = kWireHeaderBytes + (int64_t)h.payload;
+    if (!dst) {
+        *bytes = total;
+        return false;
+    }
+    if (*bytes < total) throw_err(AESFHE_EARG, "buffer of %lld bytes, the blob has %lld", (long long)*bytes, (long long)total);
+    *bytes = total;
+    return true;
+}
+
+// the fused pack launch of src ([groups][polys][nl][N]) and the one copy of the packed bytes
+static void wire_pack_run(aesfhe_engine* e, const WireHeader& h, const WireShape& s, const u64* src, const u64* sec, u64 gal, void* dst) {
+    wire_header_write(h, (uint8_t*)dst);
+    if (!h.payload) return;
+    const int N = e->N;
+    const long wpp = (long)(wire_sumw(e->chain.q.data(), s.nl) << (e->logN - 6));
+    Tmp packed(e, h.payload / 8);
+    {
+        const double rows = (double)s.groups * s.packed * s.nl * N * 8.0;
+        ProfScope pr(e, FAM_EW, rows * (sec ? 3 : 1) + (double)h.payload, "wire_pack");
+        hipLaunchKernelGGL(k_wire_pack, dim3(N / kWireTile, s.nl, s.groups * s.packed), dim3(kWireThreads), 0, e->stream, src, s.polys, s.packed,
+                           s.nl, wpp, sec, gal, wire_key(h.seed), derive(derive(kWireTag, wire_label_kind(h)), h.galois), packed.p,
+                           (const u64*)e->q, (const double*)e->qinv, e->logN);
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync((uint8_t*)dst + kWireHeaderBytes, packed.p, h.payload, hipMemcpyDeviceToHost, e->stream));
+    HIPC(hipStreamSynchronize(e->stream));
+}
+
+// One copy of the packed bytes to the device and the fused unpack launch into dst; AESFHE_EARG when
+// a residue is not canonical (the caller's object is dropped by its owner).
+static void wire_unpack_run(aesfhe_engine* e, const WireHeader& h, const WireShape& s, const void* src, u64* dst) {
+    const int N = e->N;
+    const long wpp = (long)(wire_sumw(e->chain.q.data(), s.nl) << (e->logN - 6));
+    Tmp packed(e, h.payload / 8 + 1), flag(e, 1);
+    if (h.payload) HIPC(hipMemcpyAsync(packed.p, (const uint8_t*)src + kWireHeaderBytes, h.payload, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemsetAsync(flag.p, 0, 8, e->stream));
+    {
+        const double rows = (double)s.groups * s.polys * s.nl * N * 8.0;
+        ProfScope pr(e, FAM_EW, rows + (double)h.payload, "wire_unpack");
+        hipLaunchKernelGGL(k_wire_unpack, dim3(N / kWireTile, s.nl, s.groups * s.polys), dim3(kWireThreads), 0, e->stream, (const u64*)packed.p,
+                           s.polys, s.packed, s.nl, wpp, wire_key(h.seed), derive(derive(kWireTag, wire_label_kind(h)), h.galois), dst,
+                           (const u64*)e->q, e->logN, (unsigned long long*)flag.p);
+    }
+    HIPC(hipGetLastError());
+    u64 bad = 0;
+    HIPC(hipMemcpyAsync(&bad, flag.p, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPC(hipStreamSynchronize(e->stream));
+    if (bad) throw_err(AESFHE_EARG, "blob holds a residue that is not below its prime");
+}
+
+extern "C" int aesfhe_key_pack(aesfhe_engine* e, const aesfhe_key* k, const aesfhe_key* target, const uint8_t* seed, void* dst,
+                               int64_t* bytes) {
+    API_BEGIN
+    if (!e || !k || !bytes) throw_err(AESFHE_EARG, "null argument");
+    if (k->eng != e) throw_err(AESFHE_EARG, "key of another engine");
+    if (target) {
+        if (!seed) throw_err(AESFHE_EARG, "seeded packing needs 32 seed bytes");
+        if (k->kind == 0) throw_err(AESFHE_EARG, "a secret key has no mask to seed");
+        if (target->eng != e || target->kind != 0) throw_err(AESFHE_EARG, "seeded packing needs the secret key the rows are encrypted under");
+    }
+    const WireDims d = wire_dims(e);
+    WireHeader h = wire_header_of(e, d);
+    h.type = kWireKey, h.kind = k->kind, h.ndig = (uint32_t)k->ndig, h.galois = k->galois, h.keyseed = k->keyseed;
+    h.npoly = k->kind == 0 ? 1 : 2;
+    h.level = (k->kind == 1 ? e->Lp1 : e->np) - 1;
+    WireShape s;
+    if (!wire_pack_begin(e, d, h, s, seed, target != nullptr, dst, bytes)) return AESFHE_OK;
+    if ((size_t)s.groups * s.polys * s.nl * e->N * 8 != k->bytes) throw_err(AESFHE_EARG, "key block of %zu bytes does not match its kind", k->bytes);
+    u64 gal = 1;
+    if (target && k->kind == 5) {  // rows under sigma_{g^-1}(s), as aesfhe_key_galois_hoisted makes them
+        const u64 M = 2ULL * e->N;
+        for (u64 x = 1;; x = x * k->galois % M)
+            if (x * k->galois % M == 1) { gal = x; break; }
+    }
+    wire_pack_run(e, h, s, k->d, target ? target->d : nullptr, gal, dst);
+    API_END
+}
+
+extern "C" int aesfhe_ct_pack(aesfhe_engine* e, const aesfhe_ct* c, const aesfhe_key* sk, const uint8_t* seed, void* dst, int64_t* bytes) {
+    API_BEGIN
+    if (!e || !c || !bytes) throw_err(AESFHE_EARG, "null argument");
+    if (c->eng != e) throw_err(AESFHE_EARG, "ciphertext of another engine");
+    const bool seeded = sk != nullptr && !c->is_zero;  // a zero ciphertext is its header, seeded or not
+    if (sk) {
+        if (!seed) throw_err(AESFHE_EARG, "seeded packing needs 32 seed bytes");
+        if (sk->eng != e || sk->kind != 0) throw_err(AESFHE_EARG, "seeded packing needs the secret key");
+        if (seeded && c->np != 2) throw_err(AESFHE_EDEGREE, "Input ciphertext should have 2 polynomials");
+    }
+    const WireDims d = wire_dims(e);
+    WireHeader h = wire_header_of(e, d);
+    h.type = kWireCt, h.batch = c->B, h.npoly = c->np, h.level = c->level, h.zero = c->is_zero ? 1 : 0;
+    WireShape s;
+    if (!wire_pack_begin(e, d, h, s, seed, seeded, dst, bytes)) return AESFHE_OK;
+    wire_pack_run(e, h, s, c->d, seeded ? sk->d : nullptr, 1, dst);
+    API_END
+}
+
+// parse a blob of the given type, or AESFHE_EARG
+static void wire_unpack_begin(const aesfhe_engine* e, const void* src, int64_t bytes, uint32_t type, WireHeader& h, WireShape& s) {
+    if (e->logN < kWireMinLogN) throw_err(AESFHE_EARG, "the wire format needs N >= 1024");
+    const std::string err = wire_parse((const uint8_t*)src, bytes, wire_dims(e), h, s);
+    if (!err.empty()) throw_err(AESFHE_EARG, "cannot unpack: %s", err.c_str());
+    if (h.type != type) throw_err(AESFHE_EARG, "the blob holds a %s", h.type == kWireKey ? "key" : "ciphertext");
+}
+
+extern "C" int aesfhe_key_unpack(aesfhe_engine* e, const void* src, int64_t bytes, aesfhe_key** out) {
+    API_BEGIN
+    if (!e || !src || !out) throw_err(AESFHE_EARG, "null argument");
+    WireHeader h;
+    WireShape s;
+    wire_unpack_begin(e, src, bytes, kWireKey, h, s);
+    struct KeyFree {
+        void operator()(aesfhe_key* k) const { aesfhe_key_free(k); }
+    };
+    std::unique_ptr<aesfhe_key, KeyFree> k(key_new(e, h.kind, (size_t)s.groups * s.polys * s.nl * e->N));
+    k->galois = h.galois, k->keyseed = h.keyseed, k->ndig = (int)h.ndig;
+    wire_unpack_run(e, h, s, src, k->d);
+    *out = k.release();
+    API_END
+}
+
+extern "C" int aesfhe_ct_unpack(aesfhe_engine* e, const void* src, int64_t bytes, aesfhe_ct** out) {
+    API_BEGIN
+    if (!e || !src || !out) throw_err(AESFHE_EARG, "null argument");
+    WireHeader h;
+    WireShape s;
+    wire_unpack_begin(e, src, bytes, kWireCt, h, s);
+    if (h.zero) {
+        *out = ct_zero_new(e, h.batch, h.npoly, h.level).release();
+        return AESFHE_OK;
+    }
+    CtPtr c = ct_new(e, h.batch, h.npoly, h.level);
+    wire_unpack_run(e, h, s, src, c->d);
+    *out = c.release();
     API_END
 }
