@@ -35,12 +35,11 @@ namespace aesfhe {
 
 // the 8 forward column stages (R = 256) of the register tile x (x[a] = row 16 a + b of column c),
 // transposed through the LDS tile s (all 256 threads of the workgroup; s must not be read by any
-// thread from an earlier use -- the caller's barrier discipline), twiddles: stages 0-3 from the
-// prime's tables tg (w / q) and cw (w, Tabs::cw) -- uniform: scalar loads, no w = rint(wq q) on the
-// VALU --, 4-7 from the LDS copy twq of w / q; raw doubles stored to out
+// thread from an earlier use -- the caller's barrier discipline), twiddles (w as exact doubles,
+// Tabs::psid): stages 0-3 from the prime's table tg -- uniform: one scalar load each --, 4-7 from
+// its LDS copy tws; raw doubles stored to out
 __device__ __forceinline__ void cols256_stages_store(double (&x)[16], double q, double qi, bool big, const double* tg,
-                                                     const double* cw, const double* twq, double* s, u64* out, int b,
-                                                     int cl, int c) {
+                                                     const double* tws, double* s, u64* out, int b, int cl, int c) {
 #pragma unroll
     for (int st = 0; st < 4; st++) {
         const int m = 1 << st, hh = 8 >> st;
@@ -52,7 +51,7 @@ __device__ __forceinline__ void cols256_stages_store(double (&x)[16], double q, 
         for (int a = 0; a < 16; a++) {
             if (a & hh) continue;
             const int ti = m + (a >> (4 - st));
-            ct_fw(x[a], x[a + hh], cw[ti], tg[ti], q);
+            ct_f(x[a], x[a + hh], tg[ti], q, qi);
         }
     }
 #pragma unroll
@@ -71,7 +70,7 @@ __device__ __forceinline__ void cols256_stages_store(double (&x)[16], double q, 
 #pragma unroll
         for (int bb = 0; bb < 16; bb++) {
             if (bb & hh) continue;
-            ct_f(x[bb], x[bb + hh], twq[m + ap * (m >> 4) + (bb >> (8 - st))], q);
+            ct_f(x[bb], x[bb + hh], tws[m + ap * (m >> 4) + (bb >> (8 - st))], q, qi);
         }
     }
 #pragma unroll
@@ -94,7 +93,7 @@ __global__ __launch_bounds__(256, TT == 4 ? 2 : 3) void k_bconv_cols(BconvArgs a
     static_assert(TT == 4 || TT == 2, "4 or 2 targets per workgroup");
     static_assert(LT == 1 || LT == 2, "1 or 2 LDS tiles");
     __shared__ double s[LT][256 * kPadF];
-    __shared__ double twq[TT][256];
+    __shared__ double tws[TT][256];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
     const int cl = tid & 15, b = tid >> 4;
     const int id = blockIdx.x, x8 = id & 7, j = id >> 3;
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(256, TT == 4 ? 2 : 3) void k_bconv_cols(BconvArgs a
     // the tile's stage 4-7 twiddles into LDS (read after the first barrier of the column stages)
 #pragma unroll
     for (int m = 0; m < TT; m++)
-        if (m < nlive) twq[m][tid] = T.psif[((long)pid_of(limb_of(tau0 + m)) << logN) + tid];
+        if (m < nlive) tws[m][tid] = T.psid[((long)pid_of(limb_of(tau0 + m)) << logN) + tid];
     // A fragments of the tile (row r = (target r >> 3, byte plane (r & 3) + 4 ((r >> 2) & 1))),
     // fixed for the whole workgroup
     bc_v4i af[NSTEP];
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(256, TT == 4 ? 2 : 3) void k_bconv_cols(BconvArgs a
     // the column stages of each live target; LDS tile m % LT (LT = 2: the barrier inside the
     // stages of target m + 1 orders every read of tile m & 1 for target m before its reuse by
     // target m + 2; LT = 1: one more barrier before each reuse)
-    __syncthreads();  // twq
+    __syncthreads();  // tws
     if constexpr (MODE == 1) {
 #pragma unroll
         for (int m = 0; m < TT; m++) {
@@ -273,8 +272,8 @@ __global__ __launch_bounds__(256, TT == 4 ? 2 : 3) void k_bconv_cols(BconvArgs a
         if (LT == 1 && m > 0) __syncthreads();
         const int tl = limb_of(tau0 + m), pid = pid_of(tl);
         const double q = (double)T.q[pid], qi = T.qinv[pid];
-        cols256_stages_store(xv[m], q, qi, q >= kBigPrime, T.psif + ((long)pid << logN), T.cw + (long)pid * kColW,
-                             twq[m], s[m % LT], dst + ((long)tl << logN), b, cl, bx * 16 + cl);
+        cols256_stages_store(xv[m], q, qi, q >= kBigPrime, T.psid + ((long)pid << logN), tws[m], s[m % LT],
+                             dst + ((long)tl << logN), b, cl, bx * 16 + cl);
     }
 }
 

@@ -635,7 +635,7 @@ static void build_tables(aesfhe_engine* e) {
     const int N = e->N, np = e->np, L = e->L, K = e->K, Lp1 = e->Lp1;
     const auto& Q = e->chain.q;
     std::vector<u64> hq(Q), hpsi((size_t)np * N), hipsi((size_t)np * N), hninv(np);
-    std::vector<double> hqinv(np), hpsif((size_t)np * N), hipsif((size_t)np * N), hninvf(np);
+    std::vector<double> hqinv(np), hpsid((size_t)np * N), hipsid((size_t)np * N), hninvf(np);
     e->h_iroot.resize(np);
     for (int p = 0; p < np; p++) {
         u64 qq = Q[p];
@@ -651,8 +651,8 @@ static void build_tables(aesfhe_engine* e) {
             unsigned r = bit_reverse((unsigned)k, e->logN);
             hpsi[(size_t)p * N + k] = pw[r];
             hipsi[(size_t)p * N + k] = ipw[r];
-            hpsif[(size_t)p * N + k] = (double)pw[r] / (double)qq;
-            hipsif[(size_t)p * N + k] = (double)ipw[r] / (double)qq;
+            hpsid[(size_t)p * N + k] = (double)pw[r];  // exact: w < q < 2^51
+            hipsid[(size_t)p * N + k] = (double)ipw[r];
         }
         e->h_iroot[p] = pw[N / 2];
         hninv[p] = h_invmod((u64)N, qq);
@@ -663,41 +663,32 @@ static void build_tables(aesfhe_engine* e) {
     t.q = e->q = dev.up(hq);
     t.qinv = e->qinv = dev.up(hqinv);
     t.psi = dev.up(hpsi);
-    t.psif = dev.up(hpsif);
+    t.psid = dev.up(hpsid);
     t.ipsi = dev.up(hipsi);
-    t.ipsif = dev.up(hipsif);
+    t.ipsid = dev.up(hipsid);
     t.ninv = dev.up(hninv);
     t.ninvf = dev.up(hninvf);
-    if (fused_ntt(e)) {  // row factors psi^{+-brv(row << s)} / q, s = 0..7, [np][R][8] (ntt256f.h tw_row)
+    if (fused_ntt(e)) {  // row factors psi^{+-brv(row << s)} as doubles, s = 0..7, [np][R][8] (ntt256f.h tw_row)
         const int R = N / 256;
         std::vector<double> hr((size_t)np * R * 8), hir((size_t)np * R * 8);
         for (int p = 0; p < np; p++)
             for (int row = 0; row < R; row++)
                 for (int sh = 0; sh < 8; sh++) {
-                    hr[((size_t)p * R + row) * 8 + sh] = hpsif[(size_t)p * N + (row << sh)];
-                    hir[((size_t)p * R + row) * 8 + sh] = hipsif[(size_t)p * N + (row << sh)];
+                    hr[((size_t)p * R + row) * 8 + sh] = hpsid[(size_t)p * N + (row << sh)];
+                    hir[((size_t)p * R + row) * 8 + sh] = hipsid[(size_t)p * N + (row << sh)];
                 }
-        t.rtwf = dev.up(hr);
-        t.irtwf = dev.up(hir);
+        t.rtwd = dev.up(hr);
+        t.irtwd = dev.up(hir);
     }
     {
         std::vector<Tw> htw((size_t)np * N), hitw((size_t)np * N);
         for (size_t i = 0; i < htw.size(); i++) {
-            htw[i] = Tw{hpsi[i], hpsif[i]};
-            hitw[i] = Tw{hipsi[i], hipsif[i]};
+            const double qq = (double)Q[i / (size_t)N];
+            htw[i] = Tw{hpsi[i], (double)hpsi[i] / qq};
+            hitw[i] = Tw{hipsi[i], (double)hipsi[i] / qq};
         }
         t.tw = dev.up(htw);
         t.itw = dev.up(hitw);
-    }
-    {
-        std::vector<double> hcw((size_t)np * kColW), hicw((size_t)np * kColW);
-        for (int p = 0; p < np; p++)
-            for (int k = 0; k < kColW; k++) {
-                hcw[(size_t)p * kColW + k] = (double)hpsi[(size_t)p * N + (k < N ? k : 0)];
-                hicw[(size_t)p * kColW + k] = (double)hipsi[(size_t)p * N + (k < N ? k : 0)];
-            }
-        t.cw = dev.up(hcw);
-        t.icw = dev.up(hicw);
     }
     t.logN = e->logN;
     t.Lp1 = Lp1;

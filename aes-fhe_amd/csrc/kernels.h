@@ -72,6 +72,29 @@ __device__ __forceinline__ double fmul_rem(double a, double w, double wq, double
 __device__ __forceinline__ double fmul_rem_r(double a, double w, double wq, double q) {
     return fmul_rem(a, w, wq, q);
 }
+// The same remainder with the quotient taken from the product itself, qh = rint(p * (1/q)): needs
+// only w and the per-prime qi = 1/q (rounded), no w/q beside every constant and no w * qi for an
+// operand that has none.  Six full-rate ops again; the chain from a is one op longer (mul, mul,
+// rndne, fma, add).  Exactness as above: p - qh*q is an integer (p is one below 2^53, or a
+// multiple of its ulp >= 1) of magnitude <= |r| + |pl| < q + 2^48, so u and r = u + pl are exact
+// and r == a*w mod q.
+// Bound: p, qi and p*qi each carry one rounding of relative size 2^-53, so
+// |p*qi - a*w/q| <= 3 * 2^-53 * |a*w/q| (1 + 2^-52) and
+//     |r| <= (1/2 + eps) q,   eps = 3 * 2^-53 * |a*w/q| (1 + 2^-52)   [eps < |a*w/q| * 2^-51]
+// -- the bound of fmul_rem with an on-the-fly quotient (three roundings as well); a table w/q has
+// two (eps = 2 * 2^-53 |a*w/q|).  |r| < q whenever |a*w/q| < 2^53 / 6 = 1.33 * 2^50; at the edge of
+// the range (|a| < 2^51, w < q) eps < 3/4, |r| < 1.25q (seen: 0.93q).  Below 2^42 the engine's
+// lazy values stay under 2^8 q < 2^50 (|r| <= 0.875q, and <= 0.51q for |a| < 2^45); the larger
+// primes' fold schedules are re-derived in ntt256f.h and ks_fused.h.  Valid like fmul_rem for
+// signed |a| < 2^52, 0 <= |w| < q < 2^51.  tests/test_quotient_from_product.py restates it in
+// NumPy against Python integers.
+__device__ __forceinline__ double fmul_remq(double a, double w, double qi, double q) {
+    const double p = a * w;
+    const double pl = __builtin_fma(a, w, -p);
+    const double qh = __builtin_rint(p * qi);
+    const double u = __builtin_fma(-qh, q, p);
+    return u + pl;
+}
 // x - rint(x/q)*q for |x| < 2^53: result in [-q/2 - 1, q/2 + 1] (exact: qh*q < 2^53)
 __device__ __forceinline__ double fred(double x, double q, double qinv) {
     const double qh = __builtin_rint(x * qinv);
@@ -85,7 +108,9 @@ __device__ __forceinline__ u64 fcanon(double x, double q, double qinv) {
     r = r < 0.0 ? r + q : r;
     return (u64)__double_as_longlong(r + 4503599627370496.0) & 0xFFFFFFFFFFFFFULL;
 }
-// w from its table entry wq = w/q (w < q < 2^52): rint(wq * q) is exact, |wq*q - w| < 2^-4
+// w from a constant stored as wq = w/q (w < q < 2^52): rint(wq * q) is exact, |wq*q - w| < 2^-4.
+// Only the per-workgroup constants (pmodf, dinvf, ninvf, ...) are still stored that way; the
+// twiddle tables hold w itself.
 __device__ __forceinline__ double tw_w(double wq, double q) {
     return __builtin_rint(wq * q);
 }
@@ -119,26 +144,22 @@ __device__ __forceinline__ u64* span_ptr(const Span& s, int y, int logN, int Lp1
     return s.base + (long)(p & s.pmask) * s.pstride + ((long)l << logN);
 }
 
-constexpr int kColW = 64;  // Tabs::cw / icw entries per prime (R = 512 reads up to index 47)
-
 struct Tabs {
     const u64* q;
     const double* qinv;
     const u64* psi;      // [np][N] psi^{brv(k)}
-    const double* psif;  // psi/q
+    const double* psid;  // the same words as exact doubles (w, not w/q: fmul_remq takes its
+                         // quotient from the product), the fp64 passes' twiddles
     const u64* ipsi;     // [np][N] psi^{-brv(k)}
-    const double* ipsif;
-    const double* rtwf;   // N = 2^16 only: [np][256][8] psi^{brv(row << s)} / q (ntt256f.h)
-    const double* irtwf;  // the same for psi^{-1}
+    const double* ipsid;
+    const double* rtwd;   // N = 2^16 / 2^17: [np][R][8] psi^{brv(row << s)} as doubles (ntt256f.h)
+    const double* irtwd;  // the same for psi^{-1}
     const u64* ninv;
     const double* ninvf;
-    const struct Tw* tw;   // [np][N] {psi^{brv(k)}, psi^{brv(k)}/q} interleaved (16 B)
+    // [np][N] {psi^{brv(k)}, psi^{brv(k)}/q} interleaved (16 B): the generic integer passes
+    // below (mul_w wants w/q) -- the only readers of a w/q twiddle
+    const struct Tw* tw;
     const struct Tw* itw;  // [np][N] inverse
-    // [np][kColW] psi^{brv(k)} (cw) / psi^{-brv(k)} (icw) as exact doubles, k < kColW: the column
-    // passes' wave-uniform stages read w by scalar load beside w/q instead of recomputing
-    // w = rint(wq q) on the VALU (2 instructions per twiddle per wave; round 6)
-    const double* cw;
-    const double* icw;
     int logN;
     int Lp1;
 };
@@ -163,8 +184,7 @@ __global__ __launch_bounds__(256) void k_ntt_fwd_cols(Span src, Span dst, Tabs T
     u64* out = span_ptr(dst, blockIdx.y, T.logN, T.Lp1, pid);
     const int c0 = blockIdx.x * CW;
     const u64 q = T.q[pid];
-    const u64* W = T.psi + ((long)pid << T.logN);
-    const double* Wf = T.psif + ((long)pid << T.logN);
+    const Tw* W = T.tw + ((long)pid << T.logN);
     for (int e = threadIdx.x; e < R1 * CW; e += 256) {
         int r = e / CW, c = e - r * CW;
         s[e] = in[r * kC2 + c0 + c];
@@ -174,8 +194,9 @@ __global__ __launch_bounds__(256) void k_ntt_fwd_cols(Span src, Span dst, Tabs T
         for (int bf = threadIdx.x; bf < (R1 / 2) * CW; bf += 256) {
             int c = bf % CW, g = bf / CW;
             int i = g / t, r1 = i * 2 * t + (g - i * t), r2 = r1 + t;
-            u64 w = W[m + i];
-            double wf = Wf[m + i];
+            const Tw tw = W[m + i];
+            u64 w = tw.w;
+            double wf = tw.wq;
             u64 U = s[r1 * CW + c];
             u64 V = mul_w(s[r2 * CW + c], w, wf, q);
             s[r1 * CW + c] = add_m(U, V, q);
@@ -197,8 +218,7 @@ __global__ __launch_bounds__(256) void k_ntt_fwd_rows(Span dst, Tabs T) {
     u64* io = span_ptr(dst, blockIdx.y, T.logN, T.Lp1, pid);
     const int row0 = blockIdx.x * RW;
     const u64 q = T.q[pid];
-    const u64* W = T.psi + ((long)pid << T.logN);
-    const double* Wf = T.psif + ((long)pid << T.logN);
+    const Tw* W = T.tw + ((long)pid << T.logN);
     u64* base = io + (long)row0 * kC2;
     for (int e = threadIdx.x; e < RW * kC2; e += 256) s[e] = base[e];
     __syncthreads();
@@ -207,8 +227,9 @@ __global__ __launch_bounds__(256) void k_ntt_fwd_rows(Span dst, Tabs T) {
             int rl = bf / (kC2 / 2), g = bf - rl * (kC2 / 2);
             int i = g / t, c1 = i * 2 * t + (g - i * t), c2 = c1 + t;
             int widx = R1 * ml + (row0 + rl) * ml + i;
-            u64 w = W[widx];
-            double wf = Wf[widx];
+            const Tw tw = W[widx];
+            u64 w = tw.w;
+            double wf = tw.wq;
             u64* rowp = s + rl * kC2;
             u64 U = rowp[c1];
             u64 V = mul_w(rowp[c2], w, wf, q);
@@ -229,8 +250,7 @@ __global__ __launch_bounds__(256) void k_ntt_inv_rows(Span src, Span dst, Tabs T
     u64* out = span_ptr(dst, blockIdx.y, T.logN, T.Lp1, pid);
     const int row0 = blockIdx.x * RW;
     const u64 q = T.q[pid];
-    const u64* W = T.ipsi + ((long)pid << T.logN);
-    const double* Wf = T.ipsif + ((long)pid << T.logN);
+    const Tw* W = T.itw + ((long)pid << T.logN);
     const int N = 1 << T.logN;
     for (int e = threadIdx.x; e < RW * kC2; e += 256) s[e] = in[(long)row0 * kC2 + e];
     __syncthreads();
@@ -243,7 +263,8 @@ __global__ __launch_bounds__(256) void k_ntt_inv_rows(Span src, Span dst, Tabs T
             u64* rowp = s + rl * kC2;
             u64 U = rowp[c1], V = rowp[c2];
             rowp[c1] = add_m(U, V, q);
-            rowp[c2] = mul_w(sub_m(U, V, q), W[widx], Wf[widx], q);
+            const Tw tw = W[widx];
+            rowp[c2] = mul_w(sub_m(U, V, q), tw.w, tw.wq, q);
         }
         __syncthreads();
     }
@@ -258,8 +279,7 @@ __global__ __launch_bounds__(256) void k_ntt_inv_cols(Span dst, Tabs T) {
     u64* io = span_ptr(dst, blockIdx.y, T.logN, T.Lp1, pid);
     const int c0 = blockIdx.x * CW;
     const u64 q = T.q[pid];
-    const u64* W = T.ipsi + ((long)pid << T.logN);
-    const double* Wf = T.ipsif + ((long)pid << T.logN);
+    const Tw* W = T.itw + ((long)pid << T.logN);
     for (int e = threadIdx.x; e < R1 * CW; e += 256) {
         int r = e / CW, c = e - r * CW;
         s[e] = io[r * kC2 + c0 + c];
@@ -272,7 +292,8 @@ __global__ __launch_bounds__(256) void k_ntt_inv_cols(Span dst, Tabs T) {
             int i = g / tr, r1 = i * 2 * tr + (g - i * tr), r2 = r1 + tr;
             u64 U = s[r1 * CW + c], V = s[r2 * CW + c];
             s[r1 * CW + c] = add_m(U, V, q);
-            s[r2 * CW + c] = mul_w(sub_m(U, V, q), W[hg + i], Wf[hg + i], q);
+            const Tw tw = W[hg + i];
+            s[r2 * CW + c] = mul_w(sub_m(U, V, q), tw.w, tw.wq, q);
         }
         __syncthreads();
     }

@@ -362,16 +362,14 @@ __global__ void k_ks_inner_all(const u64* __restrict__ d, long dbs, const u64* _
     const double q = (double)qall[pid];
     const double qi = qinvall[pid];
     const int own = t <= l ? t / K : -1;  // the digit whose limbs include t (Q limbs only)
-    double kb[BM], ka[BM], kbq[BM], kaq[BM];
+    double kb[BM], ka[BM];
 #pragma unroll
     for (int j = 0; j < BM; j++) {
-        kb[j] = ka[j] = kbq[j] = kaq[j] = 0.0;
+        kb[j] = ka[j] = 0.0;
         if (j < beta) {
             const long ko = (long)j * kdig + ((long)pid << logN) + k;
             kb[j] = u2d(key[ko]);
             ka[j] = u2d(key[ko + kcomp]);
-            kbq[j] = kb[j] * qi;
-            kaq[j] = ka[j] * qi;
         }
     }
 #pragma unroll 4
@@ -382,8 +380,8 @@ __global__ void k_ks_inner_all(const u64* __restrict__ d, long dbs, const u64* _
             if (j < beta) {
                 const double e = u2d((j == own) ? d[(long)bb * dbs + ((long)t << logN) + k]
                                                 : ext[(long)j * exj + (long)bb * exs + ((long)t << logN) + k]);
-                s0 += fmul_rem(e, kb[j], kbq[j], q);
-                s1 += fmul_rem(e, ka[j], kaq[j], q);
+                s0 += fmul_remq(e, kb[j], qi, q);
+                s1 += fmul_remq(e, ka[j], qi, q);
                 if ((j & 3) == 3) {
                     s0 = fred(s0, q, qi);
                     s1 = fred(s1, q, qi);
@@ -459,8 +457,8 @@ __global__ void k_ks_inner_multi(const u64* __restrict__ d, long dbs, const u64*
 #pragma unroll
                 for (int j = 0; j < BM; j++) {
                     if (j < beta) {
-                        s0 += fmul_rem(e[j], kb[ii][j], kb[ii][j] * qi, q);
-                        s1 += fmul_rem(e[j], ka[ii][j], ka[ii][j] * qi, q);
+                        s0 += fmul_remq(e[j], kb[ii][j], qi, q);
+                        s1 += fmul_remq(e[j], ka[ii][j], qi, q);
                         if ((j & 3) == 3) {
                             s0 = fred(s0, q, qi);
                             s1 = fred(s1, q, qi);
@@ -1205,14 +1203,14 @@ __global__ void k_dot_pt(const u64* const* __restrict__ cp, const long* __restri
         }
 #pragma unroll
         for (int u = 0; u < 8; u++) {
-            acc += fmul_rem(cv[u], wv[u], wv[u] * qi, q);
+            acc += fmul_remq(cv[u], wv[u], qi, q);
             if ((u & 3) == 3) acc = fred(acc, q, qi);
         }
     }
     for (; i < n; i++) {
         const double c = u2d(cp[i][(long)bb * cbs[i] + (long)p * cps + off]);
         const double w = u2d(pp[i][off]);
-        acc += fmul_rem(c, w, w * qi, q);
+        acc += fmul_remq(c, w, qi, q);
         if ((i & 3) == 3) acc = fred(acc, q, qi);
     }
     o.ptr[(long)bb * o.bs + (long)p * o.ps + off] = fcanon(acc, q, qi);
@@ -1292,9 +1290,8 @@ __global__ void k_dot_pt_ext_multi(const u64* const* __restrict__ ep, const u64*
 #pragma unroll
         for (int j = 0; j < GM; j++) {
             if (pj[j]) {
-                const double wq = wv[j] * qi;
 #pragma unroll
-                for (int u = 0; u < BCT; u++) acc[u][j] += fmul_rem(e[u], wv[j], wq, q);
+                for (int u = 0; u < BCT; u++) acc[u][j] += fmul_remq(e[u], wv[j], qi, q);
             }
         }
         if ((i & 3) == 3) {
@@ -1394,9 +1391,8 @@ __global__ __launch_bounds__(256, OCC) void k_bsgs_terms(const u64* __restrict__
             const double f0 = fred(e0[u], q, qi), f1 = fred(e1[u], q, qi);  // |e| <= q/2 + 1
 #pragma unroll
             for (int j = 0; j < GM; j++) {
-                const double wq = wv[j] * qi;
-                acc0[u][j] += fmul_rem(f0, wv[j], wq, q);
-                acc1[u][j] += fmul_rem(f1, wv[j], wq, q);
+                acc0[u][j] += fmul_remq(f0, wv[j], qi, q);
+                acc1[u][j] += fmul_remq(f1, wv[j], qi, q);
             }
         }
     };
@@ -1451,8 +1447,8 @@ __global__ __launch_bounds__(256, OCC) void k_bsgs_terms(const u64* __restrict__
 #pragma unroll
                 for (int d = 0; d < BM; d++) {
                     if (d < beta) {
-                        a0 += fmul_rem(x[p][u][d], kb[p][d], kb[p][d] * qi, q);
-                        a1 += fmul_rem(x[p][u][d], ka[p][d], ka[p][d] * qi, q);
+                        a0 += fmul_remq(x[p][u][d], kb[p][d], qi, q);
+                        a1 += fmul_remq(x[p][u][d], ka[p][d], qi, q);
                         if ((d & 3) == 3) {
                             a0 = fred(a0, q, qi);
                             a1 = fred(a1, q, qi);

@@ -17,10 +17,13 @@
 //                     limbs), or FIN, the ModDown finish written straight into the output (the
 //                     kept limbs) -- the two launches of engine.hip ks_finish_fused.
 //
-// Ranges: the row NTT (table twiddles) leaves |x| <= 17q for q < 2^42 (folded to q/2 + 1 for larger primes
-// before the product); fmul_rem(x, key) lies in (-1.5q, 1.5q) (on-the-fly key quotient), so the
-// beta <= 12 products plus the folded initial term (<= q/2 + 1) sum below 19q < 2^47 for small
-// primes; big primes fold every 4 digits (< 6.5q < 2^53).
+// Ranges (fmul_remq, kernels.h: |r| <= (1/2 + 3 * 2^-53 |a w / q|) q): the row NTT leaves
+// |x| <= 9.4q for q < 2^42 (ntt256f.h header; folded to q/2 + 1 for larger primes before the
+// product); fmul_remq(x, key) stays within 0.51q there and within 0.69q for a big prime (folded
+// x), so the beta <= 12 products plus the folded initial term (<= q/2 + 1) sum below 7q < 2^45
+// for small primes; big primes fold every 4 digits (< 3.3q < 2^53).  The folds are where the w/q
+// form's bounds put them (17q after the row NTT, products within 1.5q, |acc| < 19q; 6.5q between
+// folds).
 #pragma once
 #include "kernels_ops.h"
 #include "ntt256f.h"
@@ -70,9 +73,9 @@ __device__ __forceinline__ void row_ntt8_stages(double (&x)[8], double* sr, int 
         const int base = ml * rt;
 #pragma unroll
         for (int j = 0; j < ml; j++) {
-            const double wq = W[base + j];
+            const double w = W[base + j];
 #pragma unroll
-            for (int k = 0; k < h; k++) ct_f(x[j * 2 * h + k], x[j * 2 * h + k + h], wq, q);
+            for (int k = 0; k < h; k++) ct_f(x[j * 2 * h + k], x[j * 2 * h + k + h], w, q, qi);
         }
     }
 #pragma unroll
@@ -92,9 +95,9 @@ __device__ __forceinline__ void row_ntt8_stages(double (&x)[8], double* sr, int 
         const int base = ml * rt + (L >> 2) * nj;
 #pragma unroll
         for (int j = 0; j < nj; j++) {
-            const double wq = W[base + j];
+            const double w = W[base + j];
 #pragma unroll
-            for (int k = 0; k < h; k++) ct_f(x[j * 2 * h + k], x[j * 2 * h + k + h], wq, q);
+            for (int k = 0; k < h; k++) ct_f(x[j * 2 * h + k], x[j * 2 * h + k + h], w, q, qi);
         }
     }
     wave_lds_sync();  // every lane has read its B elements
@@ -111,15 +114,15 @@ __device__ __forceinline__ void row_ntt8_stages(double (&x)[8], double* sr, int 
     {
         const int base = 64 * rt + 2 * L;
         const double w0 = W[base], w1 = W[base + 1];
-        ct_f(x[0], x[2], w0, q);
-        ct_f(x[1], x[3], w0, q);
-        ct_f(x[4], x[6], w1, q);
-        ct_f(x[5], x[7], w1, q);
+        ct_f(x[0], x[2], w0, q, qi);
+        ct_f(x[1], x[3], w0, q, qi);
+        ct_f(x[4], x[6], w1, q, qi);
+        ct_f(x[5], x[7], w1, q, qi);
     }
     {
         const int base = 128 * rt + 4 * L;
 #pragma unroll
-        for (int j = 0; j < 4; j++) ct_f(x[2 * j], x[2 * j + 1], W[base + j], q);
+        for (int j = 0; j < 4; j++) ct_f(x[2 * j], x[2 * j + 1], W[base + j], q, qi);
     }
     wave_lds_sync();  // every lane has read its C elements
 #pragma unroll
@@ -138,9 +141,9 @@ __device__ __forceinline__ void row_ntt8_stages(double (&x)[8], double* sr, int 
 // input first either way).
 __device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, const double* W, double q, double qi,
                                           bool big) {
-    auto gs = [&](double& a, double& b, double wq) {
-        if (big) gs_f<true>(a, b, wq, q, qi);
-        else gs_f<false>(a, b, wq, q, qi);
+    auto gs = [&](double& a, double& b, double w) {
+        if (big) gs_f<true>(a, b, w, q, qi);
+        else gs_f<false>(a, b, w, q, qi);
     };
 #pragma unroll
     for (int r = 0; r < 8; r++) sr[r8p(L + 32 * r)] = x[r];
@@ -171,9 +174,9 @@ __device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, con
         const int base = ml + (L >> 2) * nj;
 #pragma unroll
         for (int j = 0; j < nj; j++) {
-            const double wq = W[base + j];
+            const double w = W[base + j];
 #pragma unroll
-            for (int k = 0; k < h; k++) gs(x[j * 2 * h + k], x[j * 2 * h + k + h], wq);
+            for (int k = 0; k < h; k++) gs(x[j * 2 * h + k], x[j * 2 * h + k + h], w);
         }
     }
     wave_lds_sync();  // every lane has read its B elements
@@ -188,9 +191,9 @@ __device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, con
         const int ml = 1 << st, h = 4 >> st;
 #pragma unroll
         for (int j = 0; j < ml; j++) {
-            const double wq = W[ml + j];
+            const double w = W[ml + j];
 #pragma unroll
-            for (int k = 0; k < h; k++) gs(x[j * 2 * h + k], x[j * 2 * h + k + h], wq);
+            for (int k = 0; k < h; k++) gs(x[j * 2 * h + k], x[j * 2 * h + k + h], w);
         }
     }
     wave_lds_sync();  // sr is free again
@@ -200,10 +203,12 @@ __device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, con
 // rescale): no tensor ciphertext exists.  On the Q limbs the prologue reads a0, a1, b0, b1 and
 // forms d0 = a0 b0, d1 = a0 b1 + a1 b0 (the addend, times P) and d2 = a1 b1 (the own digit's limb,
 // times its key words) for the lane's 8 elements of (limb t, row), so the own digit is skipped in
-// the loop; addend = a, d = unused, pb = b.  Products by fmul_rem with the on-the-fly quotient, as
-// the key products: congruent, not canonical, |x| < 3q before the P / key product.  fac (optional;
-// aesfhe_mul_fma): per-prime {alpha, C, K}; the product becomes alpha (a (x) b) + C (c0, c1, 0) +
-// (K, 0, 0) (pc = c, absent: no C term), |x| < 4.5q + K before the P / key product.  FMA
+// the loop; addend = a, d = unused, pb = b.  Products by fmul_remq (the quotient from the product:
+// an operand word needs no w * (1/q)), as the key products: congruent, not canonical, |x| <= 1.75q
+// before the P / key product (canonical operands: each product within 0.875q; w/q form 3q).  fac
+// (optional; aesfhe_mul_fma): per-prime {alpha, C, K}; the product becomes alpha (a (x) b) +
+// C (c0, c1, 0) + (K, 0, 0) (pc = c, absent: no C term), |x| < 2.1q + K before the P / key product
+// (alpha times 1.75q: within 1.16q; the C term within 0.875q; w/q form 4.5q + K).  FMA
 // (fac != nullptr) is a template argument: with a runtime `if (fac)` inside the element loop every
 // element's 6 operand loads sat behind their own branch and wait (the ISA showed vmcnt(5)..(0) per
 // element), so the prologue's 48 loads were serialised 8 times.
@@ -224,21 +229,20 @@ __device__ __forceinline__ void ks_prod_prologue(double (&a0)[8], double (&a1)[8
     }
 #pragma unroll
     for (int r = 0; r < 8; r++) {
-        const double y0q = y0[r] * qi, y1q = y1[r] * qi;
-        double p0 = fmul_rem(x0[r], y0[r], y0q, q);
-        double p1 = fmul_rem(x0[r], y1[r], y1q, q) + fmul_rem(x1[r], y0[r], y0q, q);
-        double p2 = fmul_rem(x1[r], y1[r], y1q, q);
+        double p0 = fmul_remq(x0[r], y0[r], qi, q);
+        double p1 = fmul_remq(x0[r], y1[r], qi, q) + fmul_remq(x1[r], y0[r], qi, q);
+        double p2 = fmul_remq(x1[r], y1[r], qi, q);
         if constexpr (FMA) {  // multiply-add: alpha (a (x) b) + C (c0, c1, 0) + (K, 0, 0)
-            p0 = fmul_rem(p0, fal, fal * qi, q) + fK;
-            p1 = fmul_rem(p1, fal, fal * qi, q);
-            p2 = fmul_rem(p2, fal, fal * qi, q);
+            p0 = fmul_remq(p0, fal, qi, q) + fK;
+            p1 = fmul_remq(p1, fal, qi, q);
+            p2 = fmul_remq(p2, fal, qi, q);
             if (has_c) {
-                p0 += fmul_rem(u2d(xc[32 * r]), fC, fC * qi, q);
-                p1 += fmul_rem(u2d(xc[cps + 32 * r]), fC, fC * qi, q);
+                p0 += fmul_remq(u2d(xc[32 * r]), fC, qi, q);
+                p1 += fmul_remq(u2d(xc[cps + 32 * r]), fC, qi, q);
             }
         }
-        a0[r] = fmul_rem(p0, wv, f, q) + fmul_rem(p2, kb[r], kb[r] * qi, q);
-        a1[r] = fmul_rem(p1, wv, f, q) + fmul_rem(p2, ka[r], ka[r] * qi, q);
+        a0[r] = fmul_rem(p0, wv, f, q) + fmul_remq(p2, kb[r], qi, q);
+        a1[r] = fmul_rem(p1, wv, f, q) + fmul_remq(p2, ka[r], qi, q);
         if (big) {
             a0[r] = fred(a0[r], q, qi);
             a1[r] = fred(a1[r], q, qi);
@@ -291,7 +295,7 @@ __global__ __launch_bounds__(256, 4) void k_nttf_rows_ks(const u64* __restrict__
     const int row = rb * 8 + rl;
     const double q = (double)T.q[pid], qi = T.qinv[pid];
     const bool big = q >= kBigPrime;
-    const double* W = T.psif + ((long)pid << LOGN);
+    const double* W = T.psid + ((long)pid << LOGN);
     double* sr = s + rl * 288;
     // the row's 255 twiddles are the same for every digit: staged in LDS once per workgroup
     double* tw = s + 8 * 288 + rl * 256;
@@ -365,8 +369,8 @@ __global__ __launch_bounds__(256, 4) void k_nttf_rows_ks(const u64* __restrict__
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 const double kb = u2d(kbw[r]), ka = u2d(kaw[r]);
-                a0[g][r] += fmul_rem(v[r], kb, kb * qi, q);
-                a1[g][r] += fmul_rem(v[r], ka, ka * qi, q);
+                a0[g][r] += fmul_remq(v[r], kb, qi, q);
+                a1[g][r] += fmul_remq(v[r], ka, qi, q);
             }
         }
         if (big && (++nsum & 3) == 0) {
@@ -453,7 +457,7 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
     const int row = rb * 8 + rl;
     const double q = (double)T.q[pid], qi = T.qinv[pid];
     const bool big = q >= kBigPrime;
-    const double* W = T.psif + ((long)pid << LOGN);
+    const double* W = T.psid + ((long)pid << LOGN);
     double* sr = s + rl * 288;
     double* tw = s + 8 * 288 + rl * 256;
     double* ebw = s + 8 * 288 + 8 * 256 + w * 512;  // the wave's 2 rows
@@ -510,8 +514,8 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 const double v = u2d(dp[32 * r]), kb = u2d(kp[32 * r]), ka = u2d(kp[32 * r + kcomp]);
-                a0[r] += fmul_rem(v, kb, kb * qi, q);
-                a1[r] += fmul_rem(v, ka, ka * qi, q);
+                a0[r] += fmul_remq(v, kb, qi, q);
+                a1[r] += fmul_remq(v, ka, qi, q);
             }
         }
     }
@@ -555,8 +559,8 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const double kb = u2d(kbw[r]), ka = u2d(kaw[r]);
-            a0[r] += fmul_rem(v[r], kb, kb * qi, q);
-            a1[r] += fmul_rem(v[r], ka, ka * qi, q);
+            a0[r] += fmul_remq(v[r], kb, qi, q);
+            a1[r] += fmul_remq(v[r], ka, qi, q);
         }
         if (big && (++nsum & 3) == 0) {
 #pragma unroll
@@ -567,7 +571,7 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
         }
     }
     if constexpr (FIN) {
-        // ranges: |acc| < 19q and |conv| <= 17q below 2^42 (file header), so |acc - conv| < 2^48;
+        // ranges: |acc| < 7q and |conv| <= 9.4q below 2^42 (file header), so |acc - conv| < 2^47;
         // big primes fold both to q/2 + 1 first -- fmul_rem's input bound either way
         const double f = fin.dinvf[t], wv = tw_w(f, q);
         if (beta == 0 || next_digit(-1) >= beta)  // no ext digit: conv row 0 not requested yet
@@ -597,7 +601,7 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
     }
     // INV: the row's inverse twiddles replace its forward ones in LDS (the row's own 32 lanes;
     // row_ntt8_stages ended with a wave barrier, so every forward read is done)
-    const double* IW = T.ipsif + ((long)pid << LOGN);
+    const double* IW = T.ipsid + ((long)pid << LOGN);
 #pragma unroll
     for (int m = 0; m < 8; m++) {
         const int e = L + 32 * m;

@@ -3,18 +3,27 @@
 // Same data movement as ntt256.h (register-resident 256-point sub-transforms, 16 lanes x 16
 // registers, one LDS transpose per pass), but every residue is carried as an exact integer in
 // a double and every butterfly is full-rate fp64 (fmul_rem, kernels.h): ~11 VALU ops instead of
-// ~30 mixed integer ops with six quarter-rate 32-bit multiplies.  Twiddles are read as w/q only
-// (8 B, Tabs::psif / ipsif) and w = rint(wq * q) is recovered exactly (|wq*q - w| < 2^-4).
+// ~30 mixed integer ops with six quarter-rate 32-bit multiplies.  Twiddles are read as w (8 B,
+// an exact double: Tabs::psid / ipsid) and the butterfly takes its quotient from the product
+// (fmul_remq, kernels.h): no w/q beside the table and no w = rint(wq * q) per twiddle.
 //
-// Ranges (fmul_rem needs |input| < 2^51, fred needs |x| < 2^53):
-//   forward CT   x' = x + v, y' = x - v with v in (-q, q) (table twiddles: column passes, the
-//                fused key-switch pass) or (-1.5q, 1.5q) (generated twiddles, tw_row: the
-//                standalone row passes): primes < 2^42 grow to at most 9q + 8 * 1.5q = 21q over
-//                both passes; larger primes are folded (fred, |x| <= q/2+1) before every second
-//                stage (fmul_rem inputs <= 2q).
-//   inverse GS   x' = x + y doubles per stage, y' = (x - y) w in (-1.5q, 1.5q): primes < 2^42
-//                reach at most 2^8 q per pass (the column pass starts folded); for larger primes
-//                the sum output is folded in every butterfly (inputs <= q, differences <= 2.5q).
+// Ranges (fmul_remq needs |input| < 2^52, fred needs |x| < 2^53).  v = fmul_remq(y, w) has
+// |v| <= (1/2 + eps) q with eps = 3 * 2^-53 |y w / q| <= 0.375 |y| / 2^50, for table and
+// generated twiddles alike (a generated twiddle is itself a remainder of two words < q:
+// |w| <= 0.875q).  The folds are where the w/q form had them (its bounds: |v| < q from a table
+// w/q, < 1.5q from a generated one):
+//   forward CT   x' = x + v, y' = x - v.  Primes < 2^42: |y| < 2^47 gives |v| <= 0.52q per stage,
+//                from canonical inputs to at most q + 16 * 0.52q < 9.4q over both passes (w/q
+//                form: 9q + 8 * 1.5q = 21q).  Larger primes (q < 2^50) are folded (fred,
+//                |x| <= q/2 + 1) before every second stage: |v| <= 0.69q then <= 0.95q, so
+//                |x| <= 2.2q at the next fold; the R = 256 column pass starts canonical and runs
+//                two stages first: |v| <= 0.875q, then 1.21q, |x| <= 3.1q (w/q form: 3q).
+//   inverse GS   x' = x + y doubles per stage, y' = (x - y) w.  Primes < 2^42 reach at most
+//                2^8 q < 2^50 per pass (the column pass starts folded), |y'| <= 0.875q.  For
+//                larger primes the sum is folded in every butterfly; a difference of two earlier
+//                y' grows as b' = 1/2 + 0.75 b from 0.875q: |y'| <= 1.85q and |x - y| <= 3.6q
+//                < 2^52 after a pass's 8 stages (w/q form: q and 2q with table twiddles) -- every
+//                step is still exact, and the next reader folds.
 // The branch on the prime size is block-uniform (one prime per block).  Between the two passes
 // of a transform the intermediate is stored as raw doubles; final outputs are canonical u64
 // residues in [0, q), so results are identical to ntt256.h and to the oracle residue for residue.
@@ -27,45 +36,32 @@ namespace aesfhe {
 
 // kBigPrime (2^42): defined in kernels.h
 
-__device__ __forceinline__ void ct_f(double& x, double& y, double wq, double q) {
-    const double v = fmul_rem(y, tw_w(wq, q), wq, q);
+// CT / GS butterflies; w is an exact integer, |w| < q: a table entry or a generated twiddle
+__device__ __forceinline__ void ct_f(double& x, double& y, double w, double q, double qi) {
+    const double v = fmul_remq(y, w, qi, q);
     const double t = x;
     x = t + v;
     y = t - v;
 }
 template <bool FOLD>
-__device__ __forceinline__ void gs_f(double& x, double& y, double wq, double q, double qi) {
+__device__ __forceinline__ void gs_f(double& x, double& y, double w, double q, double qi) {
     const double s = x + y, d = x - y;
     x = FOLD ? fred(s, q, qi) : s;
-    y = fmul_rem(d, tw_w(wq, q), wq, q);
-}
-// CT / GS butterflies with an on-the-fly twiddle (w exact, |w| < q; wq = w * (1/q) rounded
-// twice, so fmul_rem's remainder is within 1.5q instead of q)
-__device__ __forceinline__ void ct_fw(double& x, double& y, double w, double wq, double q) {
-    const double v = fmul_rem(y, w, wq, q);
-    const double t = x;
-    x = t + v;
-    y = t - v;
-}
-template <bool FOLD>
-__device__ __forceinline__ void gs_fw(double& x, double& y, double w, double wq, double q, double qi) {
-    const double s = x + y, d = x - y;
-    x = FOLD ? fred(s, q, qi) : s;
-    y = fmul_rem(d, w, wq, q);
+    y = fmul_remq(d, w, qi, q);
 }
 // Row-pass twiddles without the N-entry table walk.  The row pass's stage with group size
 // ml = 2^s (m = 256 ml) uses psi^{brv(m + i)}, i = ml * row + j (j < ml); the three bit fields
 // of m + i are disjoint, so brv is additive and
 //     psi^{brv(256 ml + ml row + j)} = psi^{brv(256 ml + j)} * psi^{brv(row << s)}
 // = (a table entry shared by every row: 255 per prime, cache-resident) x (a per-row factor,
-// Tabs::rtwf[pid][row][s]).  Walking the N-entry table instead reads as many bytes as the limb
+// Tabs::rtwd[pid][row][s]).  Walking the N-entry table instead reads as many bytes as the limb
 // (the row passes' reads are 1.5-1.9x their writes): the standalone row passes run 5-16 %
 // faster generated (tools/ntt_q_bench.hip: 87.6 vs 104 us over 468 limbs), at +1 modular
 // product per twiddle.
-__device__ __forceinline__ void tw_row(const double* W, int idx, double rq, double q, double qi,
-                                       double& w, double& wq) {
-    w = fmul_rem(tw_w(W[idx], q), tw_w(rq, q), rq, q);
-    wq = w * qi;
+// (both factors are table words < q, so the product's remainder is the twiddle itself: signed,
+// |w| <= (1/2 + 3 * 2^-53 q) q <= 0.875q)
+__device__ __forceinline__ double tw_row(const double* W, int idx, double rw, double q, double qi) {
+    return fmul_remq(W[idx], rw, qi, q);
 }
 __device__ __forceinline__ double ld_d(const u64* p) { return __longlong_as_double((long long)*p); }
 // raw-double intermediates between NTT passes are streamed (nontemporal): one pass writes far more
@@ -91,7 +87,7 @@ __device__ __forceinline__ void wave_sync_lds() {
 // 256 rows) pairs the two 256-row halves in registers; each half is then an independent
 // 256-point column transform whose stage-m twiddles sit at m (2 + h) + group (half h, group
 // within the half), so the R = 256 code runs on each half with the index multiplier 2 + h.
-// (the body takes the 16-column block bx of span limb by and LDS s[256 * kPadF], twq[R]; a
+// (the body takes the 16-column block bx of span limb by and LDS s[256 * kPadF], tws[R]; a
 // caller that loops over blocks separates them with a workgroup barrier)
 // SPREAD (the rescale's spread in the copy-in, engine.hip rescale_view): limb y = (p, i) of dst
 // is not read from a span but formed from poly p's dropped top limb x[p] (canonical mod q_l, INTT
@@ -109,7 +105,7 @@ struct SpreadSrc {
 };
 template <int R, int SPREAD = 0>
 __device__ __forceinline__ void nttf_fwd_cols_body(const Span& src, const Span& dst, const Tabs& T, int bx, int by,
-                                                   double* s, double* twq, const SpreadSrc& ss = SpreadSrc{}) {
+                                                   double* s, double* tws, const SpreadSrc& ss = SpreadSrc{}) {
     static_assert(R == 256 || R == 512, "rows of 256: N = 2^16 or 2^17");
     constexpr int H = R / 256;
     int pid;
@@ -119,10 +115,9 @@ __device__ __forceinline__ void nttf_fwd_cols_body(const Span& src, const Span& 
     const int c = bx * 16 + cl;
     const double q = (double)T.q[pid], qi = T.qinv[pid];
     const bool big = q >= kBigPrime;
-    const double* tg = T.psif + ((long)pid << T.logN);
-    const double* cw = T.cw + (long)pid * kColW;
+    const double* tg = T.psid + ((long)pid << T.logN);
 #pragma unroll
-    for (int h = 0; h < H; h++) twq[tid + 256 * h] = tg[tid + 256 * h];
+    for (int h = 0; h < H; h++) tws[tid + 256 * h] = tg[tid + 256 * h];
     double x[16 * H];
 #pragma unroll
     for (int h = 0; h < H; h++)
@@ -140,9 +135,9 @@ __device__ __forceinline__ void nttf_fwd_cols_body(const Span& src, const Span& 
         }
     __syncthreads();
     if (H == 2) {  // stage m = 1 across the halves: canonical in, (-q, 2q) out
-        const double w = cw[1], wq = tg[1];
+        const double w = tg[1];
 #pragma unroll
-        for (int a = 0; a < 16; a++) ct_fw(x[a], x[16 + a], w, wq, q);
+        for (int a = 0; a < 16; a++) ct_f(x[a], x[16 + a], w, q, qi);
     }
 #pragma unroll
     for (int h = 0; h < H; h++) {
@@ -158,8 +153,8 @@ __device__ __forceinline__ void nttf_fwd_cols_body(const Span& src, const Span& 
 #pragma unroll
             for (int a = 0; a < 16; a++) {
                 if (a & hh) continue;
-                const int ti = m * mul + (a >> (4 - st));  // uniform: scalar loads of w and w/q
-                ct_fw(xh[a], xh[a + hh], cw[ti], tg[ti], q);
+                const int ti = m * mul + (a >> (4 - st));  // uniform: one scalar load per twiddle
+                ct_f(xh[a], xh[a + hh], tg[ti], q, qi);
             }
         }
         if (h > 0) __syncthreads();  // the previous half's LDS reads are done
@@ -179,7 +174,7 @@ __device__ __forceinline__ void nttf_fwd_cols_body(const Span& src, const Span& 
 #pragma unroll
             for (int bb = 0; bb < 16; bb++) {
                 if (bb & hh) continue;
-                ct_f(xh[bb], xh[bb + hh], twq[m * mul + ap * (m >> 4) + (bb >> (8 - st))], q);
+                ct_f(xh[bb], xh[bb + hh], tws[m * mul + ap * (m >> 4) + (bb >> (8 - st))], q, qi);
             }
         }
 #pragma unroll
@@ -189,14 +184,14 @@ __device__ __forceinline__ void nttf_fwd_cols_body(const Span& src, const Span& 
 template <int R = 256>
 __global__ __launch_bounds__(256) void k_nttf_fwd_cols(Span src, Span dst, Tabs T) {
     __shared__ double s[256 * kPadF];
-    __shared__ double twq[R];
-    nttf_fwd_cols_body<R>(src, dst, T, blockIdx.x, blockIdx.y, s, twq);
+    __shared__ double tws[R];
+    nttf_fwd_cols_body<R>(src, dst, T, blockIdx.x, blockIdx.y, s, tws);
 }
 template <int R, int SPREAD>
 __global__ __launch_bounds__(256) void k_nttf_fwd_cols_spread(SpreadSrc ss, Span dst, Tabs T) {
     __shared__ double s[256 * kPadF];
-    __shared__ double twq[R];
-    nttf_fwd_cols_body<R, SPREAD>(dst, dst, T, blockIdx.x, blockIdx.y, s, twq, ss);
+    __shared__ double tws[R];
+    nttf_fwd_cols_body<R, SPREAD>(dst, dst, T, blockIdx.x, blockIdx.y, s, tws, ss);
 }
 
 // ModDown finish fused into the row pass of the conv NTT (key switch): limb y of
@@ -236,13 +231,12 @@ __device__ __forceinline__ void row_ntt_fwd_stages(double (&x)[16], double* sr, 
 #pragma unroll
             for (int a = 0; a < 16; a++) x[a] = fred(x[a], q, qi);
         }
-        const double rq = R[st];
+        const double rw = R[st];
 #pragma unroll
         for (int j = 0; j < ml; j++) {  // butterflies of twiddle j: a = j * 2h + k, k < h
-            double w, wq;
-            tw_row(W, RR * ml + j, rq, q, qi, w, wq);
+            const double w = tw_row(W, RR * ml + j, rw, q, qi);
 #pragma unroll
-            for (int k = 0; k < h; k++) ct_fw(x[j * 2 * h + k], x[j * 2 * h + k + h], w, wq, q);
+            for (int k = 0; k < h; k++) ct_f(x[j * 2 * h + k], x[j * 2 * h + k + h], w, q, qi);
         }
     }
 #pragma unroll
@@ -258,13 +252,12 @@ __device__ __forceinline__ void row_ntt_fwd_stages(double (&x)[16], double* sr, 
 #pragma unroll
             for (int bb = 0; bb < 16; bb++) x[bb] = fred(x[bb], q, qi);
         }
-        const double rq = R[st];
+        const double rw = R[st];
 #pragma unroll
         for (int j = 0; j < nj; j++) {  // bb = j * 2h + k, k < h
-            double w, wq;
-            tw_row(W, RR * ml + ap * nj + j, rq, q, qi, w, wq);
+            const double w = tw_row(W, RR * ml + ap * nj + j, rw, q, qi);
 #pragma unroll
-            for (int k = 0; k < h; k++) ct_fw(x[j * 2 * h + k], x[j * 2 * h + k + h], w, wq, q);
+            for (int k = 0; k < h; k++) ct_f(x[j * 2 * h + k], x[j * 2 * h + k + h], w, q, qi);
         }
     }
 }
@@ -295,8 +288,8 @@ __device__ __forceinline__ void nttf_fwd_rows_body(const Span& dst, const Tabs& 
     const int row = bx * 16 + rl;
     const double q = (double)T.q[pid], qi = T.qinv[pid];
     const bool big = q >= kBigPrime;
-    const double* W = T.psif + ((long)pid << T.logN);
-    const double* Rf = T.rtwf + (long)pid * R * 8 + row * 8;
+    const double* W = T.psid + ((long)pid << T.logN);
+    const double* Rf = T.rtwd + (long)pid * R * 8 + row * 8;
     double x[16];
     double* sr = s + rl * 16 * kPadF;
     const int ap = b;
@@ -367,7 +360,7 @@ __global__ __launch_bounds__(256, 4) void k_nttf_inv_rows(Span src, Span dst, Ta
     const int row = blockIdx.x * 16 + rl;
     const double q = (double)T.q[pid], qi = T.qinv[pid];
     const bool big = q >= kBigPrime;
-    const double* W = T.ipsif + ((long)pid << T.logN);
+    const double* W = T.ipsid + ((long)pid << T.logN);
     const u64* gb = in + (long)blockIdx.x * 16 * 256;
     {  // wave w loads its rows 4w .. 4w + 3 (coalesced), element e = 1024 w + 64 k + lane
         const int e0 = (tid >> 6) * 1024 + (tid & 63);
@@ -379,8 +372,8 @@ __global__ __launch_bounds__(256, 4) void k_nttf_inv_rows(Span src, Span dst, Ta
             for (int k = 0; k < 16; k++) {
                 const int e = e0 + 64 * k;
                 const double y = u2d(gb2[e]);
-                double v = fmul_rem(u2d(gb[e]), y, y * qi, q);
-                if (FMA) v = fmul_rem(v, al, al * qi, q);
+                double v = fmul_remq(u2d(gb[e]), y, qi, q);
+                if (FMA) v = fmul_remq(v, al, qi, q);
                 s[row_tile_idx(e)] = u2d(fcanon(v, q, qi));
             }
         } else {
@@ -397,19 +390,18 @@ __global__ __launch_bounds__(256, 4) void k_nttf_inv_rows(Span src, Span dst, Ta
     double x[16];
 #pragma unroll
     for (int bb = 0; bb < 16; bb++) x[bb] = sr[ap * kPadF + bb];
-    const double* R = T.irtwf + (long)pid * RR * 8 + row * 8;
+    const double* R = T.irtwd + (long)pid * RR * 8 + row * 8;
     auto stages_lo = [&](auto fold) {
 #pragma unroll
         for (int st = 0; st < 4; st++) {
             const int t = 1 << st, ml = 128 / t, nj = 8 / t;  // group size ml = 2^(7 - st)
-            const double rq = R[7 - st];
+            const double rw = R[7 - st];
 #pragma unroll
             for (int j = 0; j < nj; j++) {  // butterflies of twiddle j: bb = j * 2t + k, k < t
-                double w, wq;
-                tw_row(W, RR * ml + ap * nj + j, rq, q, qi, w, wq);
+                const double w = tw_row(W, RR * ml + ap * nj + j, rw, q, qi);
 #pragma unroll
                 for (int k = 0; k < t; k++)
-                    gs_fw<decltype(fold)::value>(x[j * 2 * t + k], x[j * 2 * t + k + t], w, wq, q, qi);
+                    gs_f<decltype(fold)::value>(x[j * 2 * t + k], x[j * 2 * t + k + t], w, q, qi);
             }
         }
     };
@@ -424,14 +416,13 @@ __global__ __launch_bounds__(256, 4) void k_nttf_inv_rows(Span src, Span dst, Ta
 #pragma unroll
         for (int st = 4; st < 8; st++) {
             const int t = 1 << st, ta = t >> 4, ml = 128 / t;
-            const double rq = R[7 - st];
+            const double rw = R[7 - st];
 #pragma unroll
             for (int j = 0; j < ml; j++) {  // a = j * 2ta + k, k < ta
-                double w, wq;
-                tw_row(W, RR * ml + j, rq, q, qi, w, wq);
+                const double w = tw_row(W, RR * ml + j, rw, q, qi);
 #pragma unroll
                 for (int k = 0; k < ta; k++)
-                    gs_fw<decltype(fold)::value>(x[j * 2 * ta + k], x[j * 2 * ta + k + ta], w, wq, q, qi);
+                    gs_f<decltype(fold)::value>(x[j * 2 * ta + k], x[j * 2 * ta + k + ta], w, q, qi);
             }
         }
     };
@@ -454,17 +445,16 @@ __global__ __launch_bounds__(256) void k_nttf_inv_cols(Span dst, Tabs T, const d
     static_assert(R == 256 || R == 512, "rows of 256: N = 2^16 or 2^17");
     constexpr int H = R / 256;
     __shared__ double s[256 * kPadF];
-    __shared__ double twq[R];
+    __shared__ double tws[R];
     int pid;
     u64* io = span_ptr(dst, blockIdx.y, T.logN, T.Lp1, pid);
     const int tid = threadIdx.x, cl = tid & 15, b = tid >> 4;
     const int c = blockIdx.x * 16 + cl;
     const double q = (double)T.q[pid], qi = T.qinv[pid];
     const bool big = q >= kBigPrime;
-    const double* tg = T.ipsif + ((long)pid << T.logN);
-    const double* icw = T.icw + (long)pid * kColW;
+    const double* tg = T.ipsid + ((long)pid << T.logN);
 #pragma unroll
-    for (int h = 0; h < H; h++) twq[tid + 256 * h] = tg[tid + 256 * h];
+    for (int h = 0; h < H; h++) tws[tid + 256 * h] = tg[tid + 256 * h];
     const int ap = b;
     double x[16 * H];
 #pragma unroll
@@ -484,7 +474,7 @@ __global__ __launch_bounds__(256) void k_nttf_inv_cols(Span dst, Tabs T, const d
 #pragma unroll
                 for (int bb = 0; bb < 16; bb++) {
                     if (bb & tr) continue;
-                    gs_f<decltype(fold)::value>(xh[bb], xh[bb + tr], twq[base + (bb >> (st + 1))], q, qi);
+                    gs_f<decltype(fold)::value>(xh[bb], xh[bb + tr], tws[base + (bb >> (st + 1))], q, qi);
                 }
             }
         };
@@ -504,8 +494,8 @@ __global__ __launch_bounds__(256) void k_nttf_inv_cols(Span dst, Tabs T, const d
 #pragma unroll
                 for (int a = 0; a < 16; a++) {
                     if (a & ta) continue;
-                    const int ti = base + (a >> (st - 3));  // uniform: scalar loads of w and w/q
-                    gs_fw<decltype(fold)::value>(xh[a], xh[a + ta], icw[ti], tg[ti], q, qi);
+                    const int ti = base + (a >> (st - 3));  // uniform: one scalar load per twiddle
+                    gs_f<decltype(fold)::value>(xh[a], xh[a + ta], tg[ti], q, qi);
                 }
             }
         };
@@ -513,12 +503,12 @@ __global__ __launch_bounds__(256) void k_nttf_inv_cols(Span dst, Tabs T, const d
         else stages_hi(std::false_type{});
     }
     if (H == 2) {  // stage m = 1 across the halves (inputs folded to |x| <= q/2 + 1)
-        const double w = icw[1], wq = tg[1];
+        const double w = tg[1];
 #pragma unroll
         for (int a = 0; a < 16; a++) {
             x[a] = fred(x[a], q, qi);
             x[16 + a] = fred(x[16 + a], q, qi);
-            gs_fw<false>(x[a], x[16 + a], w, wq, q, qi);
+            gs_f<false>(x[a], x[16 + a], w, q, qi);
         }
     }
     const double nif = LF ? lf[blockIdx.y % dst.nl] : T.ninvf[pid];

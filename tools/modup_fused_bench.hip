@@ -15,7 +15,6 @@
 #include <vector>
 
 #include "../aes-fhe_amd/csrc/bconv_cols.h"
-#include "tabs_cw.h"
 using namespace aesfhe;
 #define HC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP %s line %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
@@ -77,7 +76,7 @@ int main(int argc, char** argv) {
     std::vector<double> qinv(np), psif((size_t)np * N), pc(4 * np), corr(np), sinvf(np);
     for (int i = 0; i < np; i++) {
         qinv[i] = 1.0 / (double)q[i];
-        for (int k = 0; k < N; k++) psif[(size_t)i * N + k] = (double)(rnd() % q[i]) / (double)q[i];
+        for (int k = 0; k < N; k++) psif[(size_t)i * N + k] = (double)(rnd() % q[i]);
         const u64 w32 = (1ULL << 32) % q[i];
         pc[4 * i] = (double)q[i], pc[4 * i + 1] = qinv[i], pc[4 * i + 2] = (double)w32, pc[4 * i + 3] = (double)w32 / (double)q[i];
         corr[i] = (double)(rnd() % q[i]);
@@ -116,8 +115,7 @@ int main(int argc, char** argv) {
     HC(hipMemset(dext, 0, ow * 8));
     HC(hipMemset(dext2, 0, ow * 8));
     Tabs T{};
-    T.q = dq, T.qinv = dqinv, T.psif = dpsif, T.logN = LOGN, T.Lp1 = Lp1;
-    T.cw = tools_make_cw(dpsif, dq, np, LOGN);
+    T.q = dq, T.qinv = dqinv, T.psid = dpsif, T.logN = LOGN, T.Lp1 = Lp1;
     std::vector<double> einv(16, 0.0), sinvmd(16, 0.0);  // ModDown: 1 / e_j of the sources q_30, p_0 .. p_9
     for (int j = 0; j < K + 1; j++) einv[j] = sinvmd[j] = 1.0 / (double)q[j == 0 ? l : Lp1 + j - 1];
     double* deinv = (double*)up(einv.data(), einv.size() * 8);

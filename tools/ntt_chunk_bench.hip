@@ -7,7 +7,6 @@
 #include <cstdlib>
 #include <vector>
 #include "../aes-fhe_amd/csrc/ntt256f.h"
-#include "tabs_cw.h"
 using namespace aesfhe;
 #define CK(x) do { hipError_t e_ = (x); if (e_) { printf("%s @%d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 
@@ -18,11 +17,10 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&dq, 8)); CK(hipMalloc(&dqi, 8)); CK(hipMalloc(&dw8, N * 8));
     double qi = 1.0 / q;
     CK(hipMemcpy(dq, &q, 8, hipMemcpyHostToDevice)); CK(hipMemcpy(dqi, &qi, 8, hipMemcpyHostToDevice));
-    { std::vector<double> h(N); for (int i = 0; i < N; i++) h[i] = (double)(i * 7919ULL % q) / q; CK(hipMemcpy(dw8, h.data(), N * 8, hipMemcpyHostToDevice)); }
+    { std::vector<double> h(N); for (int i = 0; i < N; i++) h[i] = (double)(i * 7919ULL % q); CK(hipMemcpy(dw8, h.data(), N * 8, hipMemcpyHostToDevice)); }
     CK(hipMalloc(&src, (size_t)L * N * 8)); CK(hipMalloc(&dst, (size_t)L * N * 8));
     CK(hipMemset(src, 0, (size_t)L * N * 8));
-    Tabs T{}; T.q = dq; T.qinv = dqi; T.psif = dw8; T.ipsif = dw8; T.logN = logN; T.Lp1 = 1;
-    T.cw = T.icw = tools_make_cw(dw8, dq, 1, logN);
+    Tabs T{}; T.q = dq; T.qinv = dqi; T.psid = dw8; T.ipsid = dw8; T.logN = logN; T.Lp1 = 1;
     hipStream_t s1, s2; CK(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking)); CK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
     std::vector<hipEvent_t> ev(1024);
     for (auto& e : ev) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));

@@ -14,7 +14,6 @@
 #include <vector>
 
 #include "../aes-fhe_amd/csrc/ntt256f.h"
-#include "tabs_cw.h"
 using namespace aesfhe;
 
 __global__ __launch_bounds__(256) void k_fused_fwd(Span src, Span mid, Tabs T, unsigned* head, unsigned* cnt,
@@ -112,17 +111,16 @@ int main(int argc, char** argv) {
         std::vector<u64> pw(N);
         pw[0] = 1;
         for (int k = 1; k < N; k++) pw[k] = h_mulmod(pw[k - 1], psi, q);
-        for (int k = 0; k < N; k++) hpsif[(size_t)p * N + k] = (double)pw[bit_reverse(k, logN)] / (double)q;
+        for (int k = 0; k < N; k++) hpsif[(size_t)p * N + k] = (double)pw[bit_reverse(k, logN)];
         for (int row = 0; row < 256; row++)
             for (int sh = 0; sh < 8; sh++) hr[(size_t)p * 2048 + row * 8 + sh] = hpsif[(size_t)p * N + (row << sh)];
     }
     Tabs T{};
     T.q = up(hq);
     T.qinv = up(hqi);
-    T.psif = up(hpsif);
-    T.rtwf = up(hr);
+    T.psid = up(hpsif);
+    T.rtwd = up(hr);
     T.logN = logN;
-    T.cw = tools_make_cw(T.psif, T.q, np, logN);
     T.Lp1 = np;
     std::vector<u64> h((size_t)limbs * N);
     std::mt19937_64 rng(7);

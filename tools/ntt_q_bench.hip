@@ -10,7 +10,6 @@
 #include <vector>
 
 #include "../aes-fhe_amd/csrc/ntt256f.h"
-#include "tabs_cw.h"
 using namespace aesfhe;
 
 // ===== experimental one-launch forward NTT kernels (not in the engine: measured slower than
@@ -50,12 +49,12 @@ __global__ __launch_bounds__(1024) void k_nttf_fwd_q(Span src, Span dst, Tabs T,
     const int tid = threadIdx.x;
     const double q = (double)T.q[pid], qi = T.qinv[pid];
     const bool big = q >= kBigPrime;
-    const double* W = T.psif + ((long)pid << 16);
+    const double* W = T.psid + ((long)pid << 16);
     double x[16];
     // ---- head: stages m = 1, 2 restricted to quarter qs; k = tid + 1024 j
     {
-        const double w1q = W[1], w1 = tw_w(w1q, q);
-        const double wsq = W[2 + (qs >> 1)], ws = tw_w(wsq, q);
+        const double w1 = W[1];
+        const double ws = W[2 + (qs >> 1)];
         const double s1 = qs >= 2 ? -1.0 : 1.0, s2 = (qs & 1) ? -1.0 : 1.0;
 #pragma unroll
         for (int j = 0; j < 16; j++) {
@@ -68,13 +67,13 @@ __global__ __launch_bounds__(1024) void k_nttf_fwd_q(Span src, Span dst, Tabs T,
                 a0 = u2d(in[k]), a1 = u2d(in[k + 16384]);
                 a2 = u2d(in[k + 32768]), a3 = u2d(in[k + 49152]);
             }
-            const double u = a0 + s1 * fmul_rem(a2, w1, w1q, q);
-            const double v = a1 + s1 * fmul_rem(a3, w1, w1q, q);
-            x[j] = u + s2 * fmul_rem(v, ws, wsq, q);
+            const double u = a0 + s1 * fmul_remq(a2, w1, qi, q);
+            const double v = a1 + s1 * fmul_remq(a3, w1, qi, q);
+            x[j] = u + s2 * fmul_remq(v, ws, qi, q);
         }
     }
     auto ctq = [&](double& xa, double& xb, double wq, double qq) {
-        if (!(MODE & 2)) ct_f(xa, xb, wq, qq);
+        if (!(MODE & 2)) ct_f(xa, xb, wq, qq, qi);
         else xa += wq;
     };
     const double* Wq = W;  // twiddle of (m', i') at 4 m' + qs m' + i' = m' (4 + qs) + i'
@@ -231,13 +230,13 @@ __global__ __launch_bounds__(512, 4) void k_nttf_fwd_q2(Span src, Span dst, Tabs
     const int t = threadIdx.x;
     const double q = (double)T.q[pid], qi = T.qinv[pid];
     const bool big = q >= kBigPrime;
-    const double* W = T.psif + ((long)pid << 16);
+    const double* W = T.psid + ((long)pid << 16);
     const int q4 = 4 + qs;  // twiddle of (m', i') is psi^{brv(m' (4 + qs) + i')}
     double x[32];
     // ---- head (stages m = 1, 2 of the full transform, restricted to quarter qs)
     {
-        const double w1q = (qs >= 2 ? -1.0 : 1.0) * W[1], w1 = tw_w(w1q, q);  // -w for s = 2, 3
-        const double wsq = ((qs & 1) ? -1.0 : 1.0) * W[2 + (qs >> 1)], ws = tw_w(wsq, q);
+        const double w1 = (qs >= 2 ? -1.0 : 1.0) * W[1];  // -w for s = 2, 3
+        const double ws = ((qs & 1) ? -1.0 : 1.0) * W[2 + (qs >> 1)];
 #pragma unroll
         for (int j = 0; j < 32; j++) {
             const int k = t + 512 * j;
@@ -249,13 +248,13 @@ __global__ __launch_bounds__(512, 4) void k_nttf_fwd_q2(Span src, Span dst, Tabs
                 a0 = u2d(in[k]), a1 = u2d(in[k + 16384]);
                 a2 = u2d(in[k + 32768]), a3 = u2d(in[k + 49152]);
             }
-            const double u = a0 + fmul_rem(a2, w1, w1q, q);
-            const double v = a1 + fmul_rem(a3, w1, w1q, q);
-            x[j] = u + fmul_rem(v, ws, wsq, q);
+            const double u = a0 + fmul_remq(a2, w1, qi, q);
+            const double v = a1 + fmul_remq(a3, w1, qi, q);
+            x[j] = u + fmul_remq(v, ws, qi, q);
         }
     }
     auto ctq = [&](double& xa, double& xb, double wq) {
-        if (!(MODE & 2)) ct_f(xa, xb, wq, q);
+        if (!(MODE & 2)) ct_f(xa, xb, wq, q, qi);
         else xa += wq;
     };
     auto fold = [&](int lo, int n) {
@@ -475,17 +474,16 @@ int main(int argc, char** argv) {
         std::vector<u64> pw(N);
         pw[0] = 1;
         for (int k = 1; k < N; k++) pw[k] = h_mulmod(pw[k - 1], psi, q);
-        for (int k = 0; k < N; k++) hpsif[(size_t)p * N + k] = (double)pw[bit_reverse(k, logN)] / (double)q;
+        for (int k = 0; k < N; k++) hpsif[(size_t)p * N + k] = (double)pw[bit_reverse(k, logN)];
         for (int row = 0; row < 256; row++)
             for (int sh = 0; sh < 8; sh++) hr[(size_t)p * 2048 + row * 8 + sh] = hpsif[(size_t)p * N + (row << sh)];
     }
     Tabs T{};
     T.q = up(hq);
     T.qinv = up(hqi);
-    T.psif = up(hpsif);
-    T.rtwf = up(hr);
+    T.psid = up(hpsif);
+    T.rtwd = up(hr);
     T.logN = logN;
-    T.cw = tools_make_cw(T.psif, T.q, np, logN);
     T.Lp1 = np;
     // limb y uses prime y % np: one "poly" per np limbs
     std::vector<u64> h((size_t)limbs * N);
