@@ -31,6 +31,8 @@
 #include "bconv_mfma.h"
 #include "ntt256f.h"
 
+#include <type_traits>
+
 namespace aesfhe {
 
 // the 8 forward column stages (R = 256) of the register tile x (x[a] = row 16 a + b of column c),
@@ -88,7 +90,19 @@ __device__ __forceinline__ void cols256_stages_store(double (&x)[16], double q, 
 // MODE (dev decomposition, tools/modup_fused_bench.hip; the engine runs 0): 1 = the conversion
 // alone (the column stages skipped, xv stored as is), 2 = the column stages alone (loads kept, the
 // MFMAs and their epilogue skipped)
-template <int NSTEP, bool YIN, bool VC = false, int PF = 1, int TT = 4, int LT = 2, int MODE = 0>
+// GUARD: how the conversion loop treats the targets past nt of a partial tile (the last tile of a
+// unit when nt % TT != 0).  1: `if (m >= nlive) break` per target in every tile,
+// which cuts each row group's epilogue into TT separately scheduled blocks (91 conditional
+// branches in the kernel; the targets' chains cannot interleave with each other or with the next
+// row group's loads and MFMAs).  2 (the engine's): a full tile -- 7 of 8 at the bench's shapes --
+// takes an unguarded loop, the 16 row groups one basic block, and a partial tile the guarded one,
+// chosen once per workgroup (two copies of the loop).  0: no guard in any tile -- a dead target's
+// xv is computed from the constants loaded unguarded for it (pid 0's prime and A rows: a finite
+// value, never stored); one copy, but hipcc then sinks the dead-capable targets' epilogues below
+// the loop into the column stages' `m < nlive` blocks and keeps every row group's MFMA results
+// alive for them: 256 VGPRs and 320-570 B of scratch.  0 and 1 are kept for the dev tool's
+// comparison only.
+template <int NSTEP, bool YIN, bool VC = false, int PF = 1, int TT = 4, int LT = 2, int MODE = 0, int GUARD = 2>
 __global__ __launch_bounds__(256, TT == 4 ? 2 : 3) void k_bconv_cols(BconvArgs a, Tabs T, int ntile) {
     static_assert(TT == 4 || TT == 2, "4 or 2 targets per workgroup");
     static_assert(LT == 1 || LT == 2, "1 or 2 LDS tiles");
@@ -162,96 +176,102 @@ __global__ __launch_bounds__(256, TT == 4 ? 2 : 3) void k_bconv_cols(BconvArgs a
 #pragma unroll
                 for (int g = 0; g < 2; g++) r[st][uu][g] = sp[st][uu][(16 * ar + 4 * w + 2 * g + (c >> 4)) * 256];
     };
+    auto convert = [&](auto guarded) {
 #pragma unroll
-    for (int p = 0; p < PF; p++) load(raw[p], p);
+        for (int p = 0; p < PF; p++) load(raw[p], p);
 #pragma unroll
-    for (int ar = 0; ar < 16; ar++) {
-        if (ar + PF < 16) load(raw[(ar + PF) % (PF + 1)], ar + PF);
-        bc_v4i bf[2][NSTEP];
-        double ys[2][NSTEP][2];  // VC: the slots' y values (a dead slot's 1/e is 0)
-#pragma unroll
-        for (int st = 0; st < NSTEP; st++)
-#pragma unroll
-            for (int uu = 0; uu < 2; uu++)
-#pragma unroll
-                for (int g = 0; g < 2; g++) {
-                    u64 yb = PF ? raw[ar % (PF + 1)][st][uu][g] : sp[st][uu][(16 * ar + 4 * w + 2 * g + (c >> 4)) * 256];
-                    if (!YIN) {
-                        const double q = sq[st][uu], f = sf[st][uu];
-                        double y = fmul_rem(u2d(yb), tw_w(f, q), f, q);
-                        y = y < 0.0 ? y + q : y;
-                        yb = (u64)__double_as_longlong(y + 4503599627370496.0) & 0xFFFFFFFFFFFFFULL;
-                    }
-                    // (a dead slot holds slot 0's word: its A bytes are zero -- bconv_row places
-                    // only live slots, and only their residue bytes -- so it adds nothing)
-                    if (VC) ys[g][st][uu] = u2d(yb);
-                    bf[g][st][2 * uu] = (int)(unsigned)yb ^ (int)0x80808080;
-                    bf[g][st][2 * uu + 1] = (int)(unsigned)(yb >> 32) ^ (int)0x80808080;
-                }
-        if constexpr (VC) {
-            // lane (c, h): group h's slots from both halves (yl[st][uu][half])
-            double yl[NSTEP][2][2];
-#pragma unroll
-            for (int st = 0; st < NSTEP; st++)
-#pragma unroll
-                for (int uu = 0; uu < 2; uu++) swap_halves(ys[0][st][uu], ys[1][st][uu], yl[st][uu][0], yl[st][uu][1]);
-            double sum = 0.0;
-#pragma unroll
-            for (int st = 0; st < NSTEP; st++)
-#pragma unroll
-                for (int hh = 0; hh < 2; hh++)
-#pragma unroll
-                    for (int uu = 0; uu < 2; uu++) {
-                        // unconditional: a dead slot's 1/e is 0 in the tables (+0 leaves the sum
-                        // unchanged), and a runtime-guarded scalar load per term cost a scalar-cache
-                        // round trip each (DESIGN 4.5's lesson)
-                        const int sl = 4 * st + 2 * hh + uu;
-                        sum = sum + yl[st][uu][hh] * ev[sl];
-                    }
-            const int vown = (int)__builtin_rint(sum);  // group h's v
-            const auto pr = __builtin_amdgcn_permlane32_swap((unsigned)vown, (unsigned)vown, false, false);
-            const int voth = (int)(h ? pr[0] : pr[1]);  // group 1 - h's v (the other half's)
-            // slot ns = 4 st + 2 hh + uu lives in lane half hh: byte 0 = v, bytes 1..7 zero
+        for (int ar = 0; ar < 16; ar++) {
+            if (ar + PF < 16) load(raw[(ar + PF) % (PF + 1)], ar + PF);
+            bc_v4i bf[2][NSTEP];
+            double ys[2][NSTEP][2];  // VC: the slots' y values (a dead slot's 1/e is 0)
 #pragma unroll
             for (int st = 0; st < NSTEP; st++)
 #pragma unroll
                 for (int uu = 0; uu < 2; uu++)
-                    if (4 * st + 2 * h + uu == a.ns) {
 #pragma unroll
-                        for (int g = 0; g < 2; g++) {
-                            bf[g][st][2 * uu] = ((g == h ? vown : voth) & 0xff) ^ (int)0x80808080;
-                            bf[g][st][2 * uu + 1] = (int)0x80808080;
+                    for (int g = 0; g < 2; g++) {
+                        u64 yb = PF ? raw[ar % (PF + 1)][st][uu][g] : sp[st][uu][(16 * ar + 4 * w + 2 * g + (c >> 4)) * 256];
+                        if (!YIN) {
+                            const double q = sq[st][uu], f = sf[st][uu];
+                            double y = fmul_rem(u2d(yb), tw_w(f, q), f, q);
+                            y = y < 0.0 ? y + q : y;
+                            yb = (u64)__double_as_longlong(y + 4503599627370496.0) & 0xFFFFFFFFFFFFFULL;
                         }
+                        // (a dead slot holds slot 0's word: its A bytes are zero -- bconv_row places
+                        // only live slots, and only their residue bytes -- so it adds nothing)
+                        if (VC) ys[g][st][uu] = u2d(yb);
+                        bf[g][st][2 * uu] = (int)(unsigned)yb ^ (int)0x80808080;
+                        bf[g][st][2 * uu + 1] = (int)(unsigned)(yb >> 32) ^ (int)0x80808080;
                     }
-        }
-        if constexpr (MODE == 2) {
+            if constexpr (VC) {
+                // lane (c, h): group h's slots from both halves (yl[st][uu][half])
+                double yl[NSTEP][2][2];
 #pragma unroll
-            for (int m = 0; m < TT; m++) xv[m][ar] = (double)(bf[0][0][0] & 0xffffff) + (double)(bf[1][NSTEP - 1][3] & 0xff);
-            continue;
-        }
-        bc_v16i acc[2];
+                for (int st = 0; st < NSTEP; st++)
 #pragma unroll
-        for (int g = 0; g < 2; g++) {
-            acc[g] = bc_v16i{};
+                    for (int uu = 0; uu < 2; uu++) swap_halves(ys[0][st][uu], ys[1][st][uu], yl[st][uu][0], yl[st][uu][1]);
+                double sum = 0.0;
 #pragma unroll
-            for (int st = 0; st < NSTEP; st++) acc[g] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[st], bf[g][st], acc[g], 0, 0, 0);
-        }
-        // epilogue (bconv_mfma.h): this half's 4 planes of target m, group g, as one exact double;
-        // the swap gives lane (c, h) group h's column c = its own coefficient of the column layout
+                for (int st = 0; st < NSTEP; st++)
 #pragma unroll
-        for (int m = 0; m < TT; m++) {
-            if (m >= nlive) break;  // block-uniform
-            double part[2];
+                    for (int hh = 0; hh < 2; hh++)
+#pragma unroll
+                        for (int uu = 0; uu < 2; uu++) {
+                            // unconditional: a dead slot's 1/e is 0 in the tables (+0 leaves the sum
+                            // unchanged), and a runtime-guarded scalar load per term cost a scalar-cache
+                            // round trip each (DESIGN 4.5's lesson)
+                            const int sl = 4 * st + 2 * hh + uu;
+                            sum = sum + yl[st][uu][hh] * ev[sl];
+                        }
+                const int vown = (int)__builtin_rint(sum);  // group h's v
+                const auto pr = __builtin_amdgcn_permlane32_swap((unsigned)vown, (unsigned)vown, false, false);
+                const int voth = (int)(h ? pr[0] : pr[1]);  // group 1 - h's v (the other half's)
+                // slot ns = 4 st + 2 hh + uu lives in lane half hh: byte 0 = v, bytes 1..7 zero
+#pragma unroll
+                for (int st = 0; st < NSTEP; st++)
+#pragma unroll
+                    for (int uu = 0; uu < 2; uu++)
+                        if (4 * st + 2 * h + uu == a.ns) {
+#pragma unroll
+                            for (int g = 0; g < 2; g++) {
+                                bf[g][st][2 * uu] = ((g == h ? vown : voth) & 0xff) ^ (int)0x80808080;
+                                bf[g][st][2 * uu + 1] = (int)0x80808080;
+                            }
+                        }
+            }
+            if constexpr (MODE == 2) {
+#pragma unroll
+                for (int m = 0; m < TT; m++) xv[m][ar] = (double)(bf[0][0][0] & 0xffffff) + (double)(bf[1][NSTEP - 1][3] & 0xff);
+                continue;
+            }
+            bc_v16i acc[2];
 #pragma unroll
             for (int g = 0; g < 2; g++) {
-                const int p01 = acc[g][4 * m] + acc[g][4 * m + 1] * 256, p23 = acc[g][4 * m + 2] + acc[g][4 * m + 3] * 256;
-                part[g] = __builtin_fma((double)p23, 65536.0, (double)p01);
+                acc[g] = bc_v16i{};
+#pragma unroll
+                for (int st = 0; st < NSTEP; st++) acc[g] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[st], bf[g][st], acc[g], 0, 0, 0);
             }
-            double lo, hi;
-            swap_halves(part[0], part[1], lo, hi);
-            xv[m][ar] = fred(lo + fmul_rem(hi, ew32[m], ef32[m], eq[m]) + ecr[m], eq[m], eqi[m]);
+            // epilogue (bconv_mfma.h): this half's 4 planes of target m, group g, as one exact double;
+            // the swap gives lane (c, h) group h's column c = its own coefficient of the column layout
+#pragma unroll
+            for (int m = 0; m < TT; m++) {
+                if (decltype(guarded)::value && m >= nlive) break;  // block-uniform
+                double part[2];
+#pragma unroll
+                for (int g = 0; g < 2; g++) {
+                    const int p01 = acc[g][4 * m] + acc[g][4 * m + 1] * 256, p23 = acc[g][4 * m + 2] + acc[g][4 * m + 3] * 256;
+                    part[g] = __builtin_fma((double)p23, 65536.0, (double)p01);
+                }
+                double lo, hi;
+                swap_halves(part[0], part[1], lo, hi);
+                xv[m][ar] = fred(lo + fmul_rem(hi, ew32[m], ef32[m], eq[m]) + ecr[m], eq[m], eqi[m]);
+            }
         }
-    }
+    };
+    if constexpr (GUARD == 0) convert(std::false_type{});
+    else if constexpr (GUARD == 1) convert(std::true_type{});
+    else if (nlive == TT) convert(std::false_type{});
+    else convert(std::true_type{});
     // the column stages of each live target; LDS tile m % LT (LT = 2: the barrier inside the
     // stages of target m + 1 orders every read of tile m & 1 for target m before its reuse by
     // target m + 2; LT = 1: one more barrier before each reuse)

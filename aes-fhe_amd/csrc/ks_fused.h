@@ -28,6 +28,8 @@
 #include "kernels_ops.h"
 #include "ntt256f.h"
 
+#include <type_traits>
+
 namespace aesfhe {
 
 // Row NTT with 8 elements per lane (32 lanes per 256-point row), so that the two accumulators of
@@ -52,16 +54,24 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 // rt: 256 + row when W is the limb's global psi table, 1 when W is the row's own LDS copy
 // (entry ml + j = the table's ml rt + j, stages ml = 1 .. 128).
+// big (q >= 2^42: the folds): a bool, tested where each fold stands (k_nttf_rows_ks, whose schedule
+// was measured in that form), or a KsBig<> constant, which leaves a body with the folds inline or
+// with none and no test of q in it (k_nttf_rows_ks_p: a per-lane test, not provably uniform to the
+// compiler, cut every row NTT into five separately scheduled regions).
+template <bool BIG>
+using KsBig = std::integral_constant<bool, BIG>;
+template <class Big>
 __device__ __forceinline__ void row_ntt8_stages(double (&x)[8], double* sr, int L, int rt, const double* W, double q,
-                                                double qi, bool big);
+                                                double qi, Big big);
 __device__ __forceinline__ void row_ntt8_fwd(double (&x)[8], const u64* rp, double* sr, int L, int rt,
                                              const double* W, double q, double qi, bool big) {
 #pragma unroll
     for (int r = 0; r < 8; r++) x[r] = ld_d(&rp[L + 32 * r]);
     row_ntt8_stages(x, sr, L, rt, W, q, qi, big);
 }
+template <class Big>
 __device__ __forceinline__ void row_ntt8_stages(double (&x)[8], double* sr, int L, int rt, const double* W, double q,
-                                                double qi, bool big) {
+                                                double qi, Big big) {
     // A: ml = 1, 2, 4 (global stages 0..2 of the pass); twiddle j = r >> (3 - st)
 #pragma unroll
     for (int st = 0; st < 3; st++) {
@@ -139,12 +149,8 @@ __device__ __forceinline__ void row_ntt8_stages(double (&x)[8], double* sr, int 
 // Raw doubles out, as k_nttf_inv_rows: inputs folded to |x| <= q/2 + 1, so below 2^42 the sums
 // reach 2^8 (q/2 + 1) < 2^50; larger primes fold every sum (the inverse column pass folds its
 // input first either way).
-__device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, const double* W, double q, double qi,
-                                          bool big) {
-    auto gs = [&](double& a, double& b, double w) {
-        if (big) gs_f<true>(a, b, w, q, qi);
-        else gs_f<false>(a, b, w, q, qi);
-    };
+template <bool BIG>
+__device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, const double* W, double q, double qi) {
 #pragma unroll
     for (int r = 0; r < 8; r++) sr[r8p(L + 32 * r)] = x[r];
     wave_lds_sync();
@@ -152,13 +158,13 @@ __device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, con
     for (int r = 0; r < 8; r++) x[r] = sr[r8p(8 * L + r)];
     // C: distance 1 (ml = 128, group 4L + j), distance 2 (ml = 64, group 2L + (r >> 2))
 #pragma unroll
-    for (int j = 0; j < 4; j++) gs(x[2 * j], x[2 * j + 1], W[128 + 4 * L + j]);
+    for (int j = 0; j < 4; j++) gs_f<BIG>(x[2 * j], x[2 * j + 1], W[128 + 4 * L + j], q, qi);
     {
         const double w0 = W[64 + 2 * L], w1 = W[64 + 2 * L + 1];
-        gs(x[0], x[2], w0);
-        gs(x[1], x[3], w0);
-        gs(x[4], x[6], w1);
-        gs(x[5], x[7], w1);
+        gs_f<BIG>(x[0], x[2], w0, q, qi);
+        gs_f<BIG>(x[1], x[3], w0, q, qi);
+        gs_f<BIG>(x[4], x[6], w1, q, qi);
+        gs_f<BIG>(x[5], x[7], w1, q, qi);
     }
     wave_lds_sync();  // every lane has read its C elements
 #pragma unroll
@@ -176,7 +182,7 @@ __device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, con
         for (int j = 0; j < nj; j++) {
             const double w = W[base + j];
 #pragma unroll
-            for (int k = 0; k < h; k++) gs(x[j * 2 * h + k], x[j * 2 * h + k + h], w);
+            for (int k = 0; k < h; k++) gs_f<BIG>(x[j * 2 * h + k], x[j * 2 * h + k + h], w, q, qi);
         }
     }
     wave_lds_sync();  // every lane has read its B elements
@@ -193,7 +199,7 @@ __device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, con
         for (int j = 0; j < ml; j++) {
             const double w = W[ml + j];
 #pragma unroll
-            for (int k = 0; k < h; k++) gs(x[j * 2 * h + k], x[j * 2 * h + k + h], w);
+            for (int k = 0; k < h; k++) gs_f<BIG>(x[j * 2 * h + k], x[j * 2 * h + k + h], w, q, qi);
         }
     }
     wave_lds_sync();  // sr is free again
@@ -211,24 +217,36 @@ __device__ __forceinline__ void row_intt8(double (&x)[8], double* sr, int L, con
 // (alpha times 1.75q: within 1.16q; the C term within 0.875q; w/q form 4.5q + K).  FMA
 // (fac != nullptr) is a template argument: with a runtime `if (fac)` inside the element loop every
 // element's 6 operand loads sat behind their own branch and wait (the ISA showed vmcnt(5)..(0) per
-// element), so the prologue's 48 loads were serialised 8 times.
-template <bool FMA>
+// element), so the prologue's 48 loads were serialised 8 times.  HAS_C (pc present) and BIG
+// (q >= 2^42) are template arguments for the same reason: tested per element they closed a block
+// after each element's products, so the 8 elements' chains could not interleave.
+template <bool FMA, bool HAS_C, bool BIG>
 __device__ __forceinline__ void ks_prod_prologue(double (&a0)[8], double (&a1)[8], const u64* kp, long kcomp,
                                                  const u64* xa, long aps, const u64* xb, long bps, const u64* xc,
-                                                 long cps, bool has_c, double wv, double f, double fal, double fC,
-                                                 double fK, double q, double qi, bool big) {
+                                                 long cps, double wv, double f, double fal, double fC, double fK,
+                                                 double q, double qi) {
+    static_assert(FMA || !HAS_C, "the addend ciphertext belongs to the multiply-add form");
     double x0[8], x1[8], y0[8], y1[8], kb[8], ka[8];
 #pragma unroll
-    for (int r = 0; r < 8; r++) {  // every operand word requested before the first product
+    for (int r = 0; r < 8; r++) {  // the operand words requested before the first product
         x0[r] = u2d(xa[32 * r]);
         x1[r] = u2d(xa[aps + 32 * r]);
         y0[r] = u2d(xb[32 * r]);
         y1[r] = u2d(xb[bps + 32 * r]);
-        kb[r] = u2d(kp[32 * r]);
-        ka[r] = u2d(kp[32 * r + kcomp]);
+        if constexpr (!FMA) {
+            kb[r] = u2d(kp[32 * r]);
+            ka[r] = u2d(kp[32 * r + kcomp]);
+        }
     }
 #pragma unroll
     for (int r = 0; r < 8; r++) {
+        // multiply-add: the key words are requested with their element (they are used last; up
+        // front beside the factors and the addend's words they cost 20-52 B of scratch at the
+        // kernel's 168 registers once the elements' chains interleave)
+        if constexpr (FMA) {
+            kb[r] = u2d(kp[32 * r]);
+            ka[r] = u2d(kp[32 * r + kcomp]);
+        }
         double p0 = fmul_remq(x0[r], y0[r], qi, q);
         double p1 = fmul_remq(x0[r], y1[r], qi, q) + fmul_remq(x1[r], y0[r], qi, q);
         double p2 = fmul_remq(x1[r], y1[r], qi, q);
@@ -236,14 +254,14 @@ __device__ __forceinline__ void ks_prod_prologue(double (&a0)[8], double (&a1)[8
             p0 = fmul_remq(p0, fal, qi, q) + fK;
             p1 = fmul_remq(p1, fal, qi, q);
             p2 = fmul_remq(p2, fal, qi, q);
-            if (has_c) {
+            if constexpr (HAS_C) {
                 p0 += fmul_remq(u2d(xc[32 * r]), fC, qi, q);
                 p1 += fmul_remq(u2d(xc[cps + 32 * r]), fC, qi, q);
             }
         }
         a0[r] = fmul_rem(p0, wv, f, q) + fmul_remq(p2, kb[r], qi, q);
         a1[r] = fmul_rem(p1, wv, f, q) + fmul_remq(p2, ka[r], qi, q);
-        if (big) {
+        if constexpr (BIG) {
             a0[r] = fred(a0[r], q, qi);
             a1[r] = fred(a1[r], q, qi);
         }
@@ -456,7 +474,6 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
     const int tid = threadIdx.x, L = tid & 31, rl = tid >> 5, lane = tid & 63, w = tid >> 6;
     const int row = rb * 8 + rl;
     const double q = (double)T.q[pid], qi = T.qinv[pid];
-    const bool big = q >= kBigPrime;
     const double* W = T.psid + ((long)pid << LOGN);
     double* sr = s + rl * 288;
     double* tw = s + 8 * 288 + rl * 256;
@@ -464,11 +481,9 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
     const double* er = ebw + (rl & 1) * 256;         // this lane's row in it
     const long woff = ((long)t << LOGN) + (long)(rb * 8 + 2 * w) * 256;  // the wave's first row
     // the first ext digit is requested before anything else: it lands while the prologue works
-    auto next_digit = [&](int j) {
-        for (j++; j < beta && j == own; j++) {
-        }
-        return j;
-    };
+    // the digit after j, the own one skipped (a select: as a loop it was a branch inside every
+    // digit iteration; past the last digit any value >= beta serves)
+    auto next_digit = [&](int j) { return j + 1 == own ? j + 2 : j + 1; };
     int jn = next_digit(-1);
     if (jn < beta) ks_dma_rows(ext + (long)jn * exj + (long)bb * exs + woff, ebw, lane);
 #pragma unroll
@@ -480,147 +495,173 @@ __global__ __launch_bounds__(256, 3) void k_nttf_rows_ks_p(const u64* __restrict
         }
     }
     const long roff = ((long)t << LOGN) + (long)row * 256 + L;
-    double a0[8], a1[8];
+    // The rest of the kernel exists twice, for a prime below 2^42 (no fold anywhere) and for a big
+    // one (its folds inline), chosen once: pid is the workgroup's, so the branch is uniform and
+    // neither body tests q again.
+    auto body = [&](auto big) {
+        constexpr bool BIG = decltype(big)::value;
+        double a0[8], a1[8];
 #pragma unroll
-    for (int r = 0; r < 8; r++) a0[r] = a1[r] = 0.0;
-    if (PROD && t <= l) {
-        const double f = pmodf[t], wv = tw_w(f, q);
-        const u64* kp = key + (long)own * kdig + ((long)pid << LOGN) + (long)row * 256 + L;
-        const u64* xa = addend.ptr + (long)(bb & addend.bmask) * addend.bs + roff;
-        const u64* xb = pb.ptr + (long)(bb & pb.bmask) * pb.bs + roff;
-        const u64* xc = pc.ptr ? pc.ptr + (long)(bb & pc.bmask) * pc.bs + roff : xb;
-        if (fac)
-            ks_prod_prologue<true>(a0, a1, kp, kcomp, xa, addend.ps, xb, pb.ps, xc, pc.ps, pc.ptr != nullptr, wv, f,
-                                   (double)fac[3 * t], (double)fac[3 * t + 1], (double)fac[3 * t + 2], q, qi, big);
-        else
-            ks_prod_prologue<false>(a0, a1, kp, kcomp, xa, addend.ps, xb, pb.ps, xc, pc.ps, false, wv, f, 0.0, 0.0, 0.0,
-                                    q, qi, big);
-    } else if (!PROD) {
-        if (pmodf && t <= l && addend.ptr) {
+        for (int r = 0; r < 8; r++) a0[r] = a1[r] = 0.0;
+        if (PROD && t <= l) {
             const double f = pmodf[t], wv = tw_w(f, q);
-            const u64* xa = addend.ptr + (long)bb * addend.bs + roff;
-            if (addend.np > 0) {
-#pragma unroll
-                for (int r = 0; r < 8; r++) a0[r] = fmul_rem(u2d(xa[32 * r]), wv, f, q);
+            const u64* kp = key + (long)own * kdig + ((long)pid << LOGN) + (long)row * 256 + L;
+            const u64* xa = addend.ptr + (long)(bb & addend.bmask) * addend.bs + roff;
+            const u64* xb = pb.ptr + (long)(bb & pb.bmask) * pb.bs + roff;
+            const u64* xc = pc.ptr ? pc.ptr + (long)(bb & pc.bmask) * pc.bs + roff : xb;
+            if (fac) {
+                const double fal = (double)fac[3 * t], fC = (double)fac[3 * t + 1], fK = (double)fac[3 * t + 2];
+                if (pc.ptr)
+                    ks_prod_prologue<true, true, BIG>(a0, a1, kp, kcomp, xa, addend.ps, xb, pb.ps, xc, pc.ps, wv, f, fal, fC,
+                                                      fK, q, qi);
+                else
+                    ks_prod_prologue<true, false, BIG>(a0, a1, kp, kcomp, xa, addend.ps, xb, pb.ps, xc, pc.ps, wv, f, fal,
+                                                       fC, fK, q, qi);
+            } else {
+                ks_prod_prologue<false, false, BIG>(a0, a1, kp, kcomp, xa, addend.ps, xb, pb.ps, xc, pc.ps, wv, f, 0.0, 0.0,
+                                                    0.0, q, qi);
             }
-            if (addend.np > 1) {
+        } else if (!PROD) {
+            if (pmodf && t <= l && addend.ptr) {
+                const double f = pmodf[t], wv = tw_w(f, q);
+                const u64* xa = addend.ptr + (long)bb * addend.bs + roff;
+                if (addend.np > 0) {
 #pragma unroll
-                for (int r = 0; r < 8; r++) a1[r] = fmul_rem(u2d(xa[addend.ps + 32 * r]), wv, f, q);
+                    for (int r = 0; r < 8; r++) a0[r] = fmul_rem(u2d(xa[32 * r]), wv, f, q);
+                }
+                if (addend.np > 1) {
+#pragma unroll
+                    for (int r = 0; r < 8; r++) a1[r] = fmul_rem(u2d(xa[addend.ps + 32 * r]), wv, f, q);
+                }
+            }
+            if (own >= 0 && own < beta) {  // the own digit's limbs: d itself, already in NTT form
+                const u64* kp = key + (long)own * kdig + ((long)pid << LOGN) + (long)row * 256 + L;
+                const u64* dp = d + (long)bb * dbs + roff;
+#pragma unroll
+                for (int r = 0; r < 8; r++) {
+                    const double v = u2d(dp[32 * r]), kb = u2d(kp[32 * r]), ka = u2d(kp[32 * r + kcomp]);
+                    a0[r] += fmul_remq(v, kb, qi, q);
+                    a1[r] += fmul_remq(v, ka, qi, q);
+                }
             }
         }
-        if (own >= 0 && own < beta) {  // the own digit's limbs: d itself, already in NTT form
-            const u64* kp = key + (long)own * kdig + ((long)pid << LOGN) + (long)row * 256 + L;
-            const u64* dp = d + (long)bb * dbs + roff;
+        if (accum) {
+            const u64* o0 = acc + (long)bb * abs_ + roff;
 #pragma unroll
             for (int r = 0; r < 8; r++) {
-                const double v = u2d(dp[32 * r]), kb = u2d(kp[32 * r]), ka = u2d(kp[32 * r + kcomp]);
-                a0[r] += fmul_remq(v, kb, qi, q);
-                a1[r] += fmul_remq(v, ka, qi, q);
+                a0[r] = fred(a0[r] + u2d(o0[32 * r]), q, qi);
+                a1[r] = fred(a1[r] + u2d(o0[acs + 32 * r]), q, qi);
             }
-        }
-    }
-    if (accum) {
-        const u64* o0 = acc + (long)bb * abs_ + roff;
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            a0[r] = fred(a0[r] + u2d(o0[32 * r]), q, qi);
-            a1[r] = fred(a1[r] + u2d(o0[acs + 32 * r]), q, qi);
-        }
-    } else if (big) {
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            a0[r] = fred(a0[r], q, qi);
-            a1[r] = fred(a1[r], q, qi);
-        }
-    }
-    wave_lds_sync();  // the row's twiddles (written by its own 32 lanes) before use
-    int nsum = 0;
-    const long coff = ((long)t << LOGN) + (long)(rb * 8 + 2 * w) * 256;
-#pragma unroll 1
-    while (jn < beta) {
-        const int j = jn;
-        ks_dma_wait();  // ext_j is in this wave's staging rows
-        double v[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) v[r] = er[L + 32 * r];
-        ks_lds_reads_done();
-        jn = next_digit(j);
-        // the next digit's row (or the FIN epilogue's first conv row) streams in during this NTT
-        if (jn < beta) ks_dma_rows(ext + (long)jn * exj + (long)bb * exs + woff, ebw, lane);
-        else if (FIN) ks_dma_rows(fin.conv + (long)bb * fin.cbs + coff, ebw, lane);
-        const u64* kp = key + (long)j * kdig + ((long)pid << LOGN) + (long)row * 256 + L;
-        u64 kbw[8], kaw[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            kbw[r] = kp[32 * r];
-            kaw[r] = kp[32 * r + kcomp];
-        }
-        row_ntt8_stages(v, sr, L, 1, tw, q, qi, big);
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const double kb = u2d(kbw[r]), ka = u2d(kaw[r]);
-            a0[r] += fmul_remq(v[r], kb, qi, q);
-            a1[r] += fmul_remq(v[r], ka, qi, q);
-        }
-        if (big && (++nsum & 3) == 0) {
+        } else if (BIG) {
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 a0[r] = fred(a0[r], q, qi);
                 a1[r] = fred(a1[r], q, qi);
             }
         }
-    }
-    if constexpr (FIN) {
-        // ranges: |acc| < 7q and |conv| <= 9.4q below 2^42 (file header), so |acc - conv| < 2^47;
-        // big primes fold both to q/2 + 1 first -- fmul_rem's input bound either way
-        const double f = fin.dinvf[t], wv = tw_w(f, q);
-        if (beta == 0 || next_digit(-1) >= beta)  // no ext digit: conv row 0 not requested yet
-            ks_dma_rows(fin.conv + (long)bb * fin.cbs + coff, ebw, lane);
+        wave_lds_sync();  // the row's twiddles (written by its own 32 lanes) before use
+        int nsum = 0;
+        const long coff = ((long)t << LOGN) + (long)(rb * 8 + 2 * w) * 256;
 #pragma unroll 1
-        for (int c = 0; c < 2; c++) {
-            ks_dma_wait();
-            double cv[8];
+        while (jn < beta) {
+            const int j = jn;
+            ks_dma_wait();  // ext_j is in this wave's staging rows
+            double v[8];
 #pragma unroll
-            for (int r = 0; r < 8; r++) cv[r] = er[L + 32 * r];
+            for (int r = 0; r < 8; r++) v[r] = er[L + 32 * r];
             ks_lds_reads_done();
-            if (c == 0) ks_dma_rows(fin.conv + (long)bb * fin.cbs + fin.cps + coff, ebw, lane);
-            row_ntt8_stages(cv, sr, L, 1, tw, q, qi, big);
-            const u64* ap = fin.add.ptr && c < fin.add.np ? fin.add.ptr + (long)bb * fin.add.bs + (long)c * fin.add.ps + roff
-                                                          : nullptr;
-            u64* op = fin.out + (long)bb * fin.obs + (long)c * fin.ops + roff;
+            jn = next_digit(j);
+            // the next digit's row (or the FIN epilogue's first conv row) streams in during this NTT
+            // (FIN always requests a row here: the address is selected, not branched on, so that
+            // the digit iteration stays one block)
+            if constexpr (FIN)
+                ks_dma_rows(jn < beta ? ext + (long)jn * exj + (long)bb * exs + woff : fin.conv + (long)bb * fin.cbs + coff,
+                            ebw, lane);
+            else if (jn < beta) ks_dma_rows(ext + (long)jn * exj + (long)bb * exs + woff, ebw, lane);
+            const u64* kp = key + (long)j * kdig + ((long)pid << LOGN) + (long)row * 256 + L;
+            u64 kbw[8], kaw[8];
 #pragma unroll
             for (int r = 0; r < 8; r++) {
-                double a = c ? a1[r] : a0[r];
-                if (big) a = fred(a, q, qi);
-                double v = fmul_rem(a - cv[r], wv, f, q);
-                if (ap) v += u2d(ap[32 * r]);
-                __builtin_nontemporal_store(fcanon(v, q, qi), &op[32 * r]);
+                kbw[r] = kp[32 * r];
+                kaw[r] = kp[32 * r + kcomp];
+            }
+            row_ntt8_stages(v, sr, L, 1, tw, q, qi, big);
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                const double kb = u2d(kbw[r]), ka = u2d(kaw[r]);
+                a0[r] += fmul_remq(v[r], kb, qi, q);
+                a1[r] += fmul_remq(v[r], ka, qi, q);
+            }
+            if (BIG && (++nsum & 3) == 0) {
+#pragma unroll
+                for (int r = 0; r < 8; r++) {
+                    a0[r] = fred(a0[r], q, qi);
+                    a1[r] = fred(a1[r], q, qi);
+                }
             }
         }
-        return;
-    }
-    // INV: the row's inverse twiddles replace its forward ones in LDS (the row's own 32 lanes;
-    // row_ntt8_stages ended with a wave barrier, so every forward read is done)
-    const double* IW = T.ipsid + ((long)pid << LOGN);
+        if constexpr (FIN) {
+            // ranges: |acc| < 7q and |conv| <= 9.4q below 2^42 (file header), so |acc - conv| < 2^47;
+            // big primes fold both to q/2 + 1 first -- fmul_rem's input bound either way
+            const double f = fin.dinvf[t], wv = tw_w(f, q);
+            if (beta == 0 || next_digit(-1) >= beta)  // no ext digit: conv row 0 not requested yet
+                ks_dma_rows(fin.conv + (long)bb * fin.cbs + coff, ebw, lane);
+#pragma unroll 1
+            for (int c = 0; c < 2; c++) {
+                ks_dma_wait();
+                double cv[8];
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-        const int e = L + 32 * m;
-        if (e > 0) {
-            const int ml = 1 << (31 - __clz(e));
-            tw[e] = IW[(long)ml * (R + row) + (e - ml)];
+                for (int r = 0; r < 8; r++) cv[r] = er[L + 32 * r];
+                ks_lds_reads_done();
+                if (c == 0) ks_dma_rows(fin.conv + (long)bb * fin.cbs + fin.cps + coff, ebw, lane);
+                row_ntt8_stages(cv, sr, L, 1, tw, q, qi, big);
+                const u64* ap = fin.add.ptr && c < fin.add.np ? fin.add.ptr + (long)bb * fin.add.bs + (long)c * fin.add.ps + roff
+                                                              : nullptr;
+                u64* op = fin.out + (long)bb * fin.obs + (long)c * fin.ops + roff;
+                // the addend's presence is tested once, not per element (a branch over each element's
+                // load): the 8 finish chains of either loop are independent instructions of one block
+                double v[8];
+#pragma unroll
+                for (int r = 0; r < 8; r++) {
+                    double a = c ? a1[r] : a0[r];
+                    if constexpr (BIG) a = fred(a, q, qi);
+                    v[r] = fmul_rem(a - cv[r], wv, f, q);
+                }
+                if (ap) {
+#pragma unroll
+                    for (int r = 0; r < 8; r++) __builtin_nontemporal_store(fcanon(v[r] + u2d(ap[32 * r]), q, qi), &op[32 * r]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 8; r++) __builtin_nontemporal_store(fcanon(v[r], q, qi), &op[32 * r]);
+                }
+            }
+            return;
         }
-    }
-    wave_lds_sync();
-    u64* o0 = acc + (long)bb * abs_ + roff;
+        // INV: the row's inverse twiddles replace its forward ones in LDS (the row's own 32 lanes;
+        // row_ntt8_stages ended with a wave barrier, so every forward read is done)
+        const double* IW = T.ipsid + ((long)pid << LOGN);
 #pragma unroll
-    for (int c = 0; c < 2; c++) {
-        double x[8];
+        for (int m = 0; m < 8; m++) {
+            const int e = L + 32 * m;
+            if (e > 0) {
+                const int ml = 1 << (31 - __clz(e));
+                tw[e] = IW[(long)ml * (R + row) + (e - ml)];
+            }
+        }
+        wave_lds_sync();
+        u64* o0 = acc + (long)bb * abs_ + roff;
 #pragma unroll
-        for (int r = 0; r < 8; r++) x[r] = fred(c ? a1[r] : a0[r], q, qi);
-        row_intt8(x, sr, L, tw, q, qi, big);
+        for (int c = 0; c < 2; c++) {
+            double x[8];
 #pragma unroll
-        for (int r = 0; r < 8; r++) st_d(&o0[(long)c * acs + 32 * r], x[r]);
-    }
+            for (int r = 0; r < 8; r++) x[r] = fred(c ? a1[r] : a0[r], q, qi);
+            row_intt8<BIG>(x, sr, L, tw, q, qi);
+#pragma unroll
+            for (int r = 0; r < 8; r++) st_d(&o0[(long)c * acs + 32 * r], x[r]);
+        }
+    };
+    if (q >= kBigPrime) body(KsBig<true>{});
+    else body(KsBig<false>{});
 }
 
 }  // namespace aesfhe

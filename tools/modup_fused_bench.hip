@@ -5,8 +5,13 @@
 // (bconv_cols.h) writing ext directly.  Every output word of the fused kernel is checked against
 // the pair mod q (the raw-double intermediates differ in representation, not in residue).
 // Constants are arbitrary but in range (random w < q twiddles, random signed-byte tables).
-//   hipcc --offload-arch=gfx950 -O3 -o tools/modup_fused_bench tools/modup_fused_bench.hip
-//   tools/modup_fused_bench [digit] [B]
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o tools/modup_fused_bench tools/modup_fused_bench.hip
+//   tools/modup_fused_bench [digit] [B] [cold|all] [variant] [l]
+// l (default 30) moves the target count, so that the last tile of a unit is partial in every way:
+// nt % 4 = 1 (digit 0, l = 30), 2 (digit 2, or ModDown at l = 30), 3 (digit 0, l = 28).  The fused
+// kernel writes into a buffer with one spare limb per (element, component) after the last target
+// -- where a dead target of the partial tile would land if it were stored -- filled with a canary
+// word that must come back untouched.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -49,7 +54,8 @@ int main(int argc, char** argv) {
     const int B = argc > 2 ? atoi(argv[2]) : 32;
     const bool only_cold = argc > 3 && !strcmp(argv[3], "cold");  // PMC runs: the cold launches only
     const bool md = digit < 0;
-    const int L = 30, K = 10, A = 12, l = 30, Lp1 = L + 1, np = Lp1 + K, ne = l + 1 + K;
+    const int L = 30, K = 10, A = 12, l = argc > 5 ? atoi(argv[5]) : 30, Lp1 = L + 1, np = Lp1 + K, ne = l + 1 + K;
+    if (l < 1 || l > L || digit * A > l) return printf("l in 1..%d, the digit within it\n", L), 1;
     const int lo = md ? 0 : digit * A, hi = md ? 0 : std::min(lo + A, l + 1);
     const int alpha = md ? K + 1 : hi - lo, nt = md ? l : ne - alpha, nc = md ? 2 : 1;
     const int nstep = (alpha + (md ? 1 : 0) + 3) / 4;
@@ -111,9 +117,14 @@ int main(int argc, char** argv) {
     const size_t ow = (size_t)B * (md ? 2 * (size_t)l * N : (size_t)neN);  // output words
     HC(hipMalloc(&dmu, ow * 8));
     HC(hipMalloc(&dext, ow * 8));
-    HC(hipMalloc(&dext2, ow * 8));
+    // the fused kernel's output: nlimb + 1 limbs per (element, component), the last one the canary
+    const int nlimb = md ? l : ne;
+    const size_t ow2 = (size_t)B * nc * (nlimb + 1) * N;
+    const u64 kCanary = 0xC0FFEE0DDBA11ULL;
+    std::vector<u64> fill(ow2);
+    for (size_t i = 0; i < ow2; i++) fill[i] = i / N % (nlimb + 1) == (size_t)nlimb ? kCanary : 0;
+    HC(hipMalloc(&dext2, ow2 * 8));
     HC(hipMemset(dext, 0, ow * 8));
-    HC(hipMemset(dext2, 0, ow * 8));
     Tabs T{};
     T.q = dq, T.qinv = dqinv, T.psid = dpsif, T.logN = LOGN, T.Lp1 = Lp1;
     std::vector<double> einv(16, 0.0), sinvmd(16, 0.0);  // ModDown: 1 / e_j of the sources q_30, p_0 .. p_9
@@ -158,10 +169,12 @@ int main(int argc, char** argv) {
         }
     };
     BconvArgs af = a;
-    af.dst = dext2;
+    af.dst = dext2, af.dcs = (long)(nlimb + 1) * N, af.dbs = nc * af.dcs;
     int pf = 1;
     // pf: 0, 1, 2 = prefetch depth with 4 targets per workgroup; 3 = PF 1, 2 targets, 2 LDS tiles;
-    // 4 = PF 1, 2 targets, 1 LDS tile
+    // 4 = PF 1, 2 targets, 1 LDS tile; 5 / 6 = MODE 1 / 2; 7 = PF 1 with the conversion loop's
+    // per-target guard in every tile (GUARD 1), 8 = PF 1 with no guard in any tile (GUARD 0);
+    // every other variant runs the engine's GUARD 2
     auto fused = [&]() {
         const int tt = pf >= 3 ? 2 : 4, nti = (nt + tt - 1) / tt;
         const dim3 g(16 * B * nc * nti);
@@ -169,8 +182,11 @@ int main(int argc, char** argv) {
                       else hipLaunchKernelGGL((k_bconv_cols<S, true, false, P, TT_, LT_>), g, dim3(256), 0, 0, af, T, nti); } while (0)
 #define FM(S, MD) do { if (md) hipLaunchKernelGGL((k_bconv_cols<S, true, true, 1, 4, 2, MD>), g, dim3(256), 0, 0, af, T, nti); \
                       else hipLaunchKernelGGL((k_bconv_cols<S, true, false, 1, 4, 2, MD>), g, dim3(256), 0, 0, af, T, nti); } while (0)
+#define FG(S, G) do { if (md) hipLaunchKernelGGL((k_bconv_cols<S, true, true, 1, 4, 2, 0, G>), g, dim3(256), 0, 0, af, T, nti); \
+                      else hipLaunchKernelGGL((k_bconv_cols<S, true, false, 1, 4, 2, 0, G>), g, dim3(256), 0, 0, af, T, nti); } while (0)
 #define FZ(S, P) do { if (P == 1 && pf == 3) FV(S, 1, 2, 2); else if (P == 1 && pf == 4) FV(S, 1, 2, 1); \
                       else if (P == 1 && pf == 5) FM(S, 1); else if (P == 1 && pf == 6) FM(S, 2); \
+                      else if (P == 1 && pf == 7) FG(S, 1); else if (P == 1 && pf == 8) FG(S, 0); \
                       else FV(S, P, 4, 2); } while (0)
 #define FS(S) do { if (pf == 0) FZ(S, 0); else if (pf == 2) FZ(S, 2); else FZ(S, 1); } while (0)  // 3..6: PF 1
         switch (nstep) {
@@ -180,22 +196,26 @@ int main(int argc, char** argv) {
         }
 #undef FS
 #undef FZ
+#undef FG
 #undef FM
 #undef FV
     };
     pair(true, true);
-    for (int chk = 0; chk <= 4 && !only_cold; chk++) {
+    for (int chk = 0; chk <= 8 && !only_cold; chk++) {
+    if (chk == 5 || chk == 6) continue;  // the decomposition modes write no comparable output
     pf = chk;
-    HC(hipMemset(dext2, 0, ow * 8));
+    HC(hipMemcpy(dext2, fill.data(), ow2 * 8, hipMemcpyHostToDevice));
     fused();
     HC(hipDeviceSynchronize());
-    {  // check: every target limb, residue equality
-        std::vector<u64> r1(ow), r2(ow);
+    {  // check: every target limb, residue equality; the canary limbs word for word
+        std::vector<u64> r1(ow), r2(ow2);
         HC(hipMemcpy(r1.data(), dext, r1.size() * 8, hipMemcpyDeviceToHost));
         HC(hipMemcpy(r2.data(), dext2, r2.size() * 8, hipMemcpyDeviceToHost));
         long bad = 0, tot = 0;
         double maxr = 0;
-        const int nlimb = md ? l : ne;
+        long touched = 0;
+        for (int bb = 0; bb < B * nc; bb++)
+            for (int k = 0; k < N; k++) touched += r2[((size_t)bb * (nlimb + 1) + nlimb) * N + k] != kCanary;
         for (int bb = 0; bb < B * nc; bb++)
             for (int tl = 0; tl < nlimb; tl++) {
                 if (!md && tl >= lo && tl < hi) continue;
@@ -203,8 +223,9 @@ int main(int argc, char** argv) {
                 const long long Q = (long long)q[pid];
                 for (int k = 0; k < N; k++) {
                     const size_t o = (size_t)bb * nlimb * N + (size_t)tl * N + k;
+                    const size_t o2 = (size_t)bb * (nlimb + 1) * N + (size_t)tl * N + k;
                     double d1, d2;
-                    memcpy(&d1, &r1[o], 8), memcpy(&d2, &r2[o], 8);
+                    memcpy(&d1, &r1[o], 8), memcpy(&d2, &r2[o2], 8);
                     const long long i1 = (long long)d1, i2 = (long long)d2;
                     maxr = std::max(maxr, std::fabs(d2) / (double)Q);
                     if ((double)i1 != d1 || (double)i2 != d2 || ((i1 - i2) % Q) != 0) {
@@ -214,8 +235,9 @@ int main(int argc, char** argv) {
                     tot++;
                 }
             }
-        printf("check V%d: %ld / %ld words differ mod q (max |fused| = %.2f q)\n", pf, bad, tot, maxr);
-        if (bad) return 1;
+        printf("check V%d: %ld / %ld words differ mod q (max |fused| = %.2f q); nt %% 4 = %d, %ld canary words touched\n",
+               pf, bad, tot, maxr, nt % 4, touched);
+        if (bad || touched) return 1;
     }
     }
     hipEvent_t e0, e1;
@@ -267,7 +289,7 @@ int main(int argc, char** argv) {
         cold(nm, fused);
         return 0;
     }
-    for (pf = 0; pf <= 6; pf++) {  // 5 / 6: the conversion alone / the column stages alone (MODE 1 / 2)
+    for (pf = 0; pf <= 8; pf++) {  // 5 / 6: the conversion alone / the column stages alone (MODE 1 / 2)
         char nm[32];
         snprintf(nm, sizeof nm, "cold fused V%d", pf);
         cold(nm, fused);
@@ -276,7 +298,7 @@ int main(int argc, char** argv) {
         timeit("bconv_mfma", [&] { pair(true, false); });
         timeit("cols", [&] { pair(false, true); });
         timeit("pair", [&] { pair(true, true); });
-        for (pf = 0; pf <= 6; pf++) {
+        for (pf = 0; pf <= 8; pf++) {
             char nm[32];
             snprintf(nm, sizeof nm, "fused V%d", pf);
             timeit(nm, fused);
