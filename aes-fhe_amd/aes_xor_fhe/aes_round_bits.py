@@ -36,6 +36,10 @@ symmetric ciphertext is folded into the last round key: same schedule, same thre
 To numbers (`AESSlicedRound.transcipher_values`): `out_level` asks the
 schedule to end round 10 with levels to spare (a fourth refresh at L = 30), the bits are cleaned
 and 8 / 16 / 32 of them are summed into one value per slot, exactly (Engine.lincomb_int).
+
+Decryption (`AESSlicedDecrypt`: decrypt_aes128 / transcipher_ecb / transcipher_cbc, DESIGN.md
+section 5.5): the equivalent inverse cipher in T-table form, at the forward round's depth, so the
+schedule and the refreshes above apply unchanged.
 """
 from __future__ import annotations
 
@@ -59,6 +63,34 @@ def walsh_sbox() -> np.ndarray:
                       for v in range(16)] for m in range(16)], dtype=np.float64)  # [mask, nibble]
     hi, lo = x >> 4, x & 15
     return np.einsum("tx,sx,ux->tsu", f, mono[:, hi], mono[:, lo]) / 256.0
+
+
+INV_MIX = (14, 11, 13, 9)  # InvMixColumns: out_r' = XOR_r INV_MIX[(r - r') mod 4] * a_r
+
+
+def _walsh_bytes(table: np.ndarray) -> np.ndarray:
+    """walsh_sbox for any byte function `table` (256 bytes): W[t, S, T] of its +-1 output bit t."""
+    x = np.arange(256)
+    f = np.stack([1.0 - 2.0 * ((np.asarray(table)[x].astype(np.int64) >> t) & 1) for t in range(8)])
+    mono = np.array([[np.prod([1 - 2 * ((v >> k) & 1) for k in range(4) if (m >> k) & 1])
+                      for v in range(16)] for m in range(16)], dtype=np.float64)  # [mask, nibble]
+    hi, lo = x >> 4, x & 15
+    W = np.einsum("tx,sx,ux->tsu", f, mono[:, hi], mono[:, lo]) / 256.0
+    assert np.array_equal(np.rint(W * 64) / 64.0, W)  # 64 W is an integer
+    return W
+
+
+def walsh_inv_sbox() -> np.ndarray:
+    """W[t, S, T] of the inverse S-box (walsh_sbox's form): (8, 16, 16)."""
+    return _walsh_bytes(T.INV_SBOX)
+
+
+def walsh_inv_tbox() -> np.ndarray:
+    """W[m, t, S, T]: bit t of INV_MIX[m] * InvS(x) in GF(2^8), the four byte functions of the
+    equivalent inverse cipher's T-table (multiples 0e, 0b, 0d, 09): (4, 8, 16, 16).  Every one is
+    a Boolean function of the byte x, hence a sum over the same 15 x 15 nibble monomials as the
+    S-box, with 64 W an integer in [-8, 8]."""
+    return np.stack([_walsh_bytes(T.GF_MUL_TABLES[c][T.INV_SBOX]) for c in INV_MIX])
 
 
 class AESRowRound:
@@ -981,3 +1013,152 @@ class AESSlicedRound(AESRowRound):
             bits = self.clean_bits(bits)
         cts, amplitude = self.values_from_bits(bits, width, byteorder, in_scale=amp)
         return cts, amplitude, refreshes
+
+
+class AESSlicedDecrypt(AESSlicedRound):
+    """AES-128 decryption on the sliced bit state: the equivalent inverse
+    cipher of FIPS-197 5.3.5 in T-table form, under the decryption keys
+    aes_tables.decryption_keys (dk_0 = k_10, dk_i = InvMixColumns(k_{10-i}), dk_10 = k_0; they go
+    through encrypt_round_key / pack_round_keys / encrypt_key_bundle / expand_round_keys like any
+    eleven 16-byte keys).
+
+    Only `round` and `final_round` differ from the forward class, and they cost the same depth
+    (7 and 5), so the scheduler, the key levels, the refreshes, clean_bits and values_from_bits
+    are inherited as they are.
+
+    * InvSubBytes + InvShiftRows + the four InvMixColumns multiples: every bit of m * InvS(x),
+      m in (0e, 0b, 0d, 09), is a Boolean function of the byte x, so one poly2_int call per row on
+      the S-box's monomials yields 32 outputs T[r][m][j] (forward: 8), depth 4, with
+      InvShiftRows, out(r, c) = in(r, c - r), folded in as slab_rot = (4 - r) mod 4.
+    * InvMixColumns + AddRoundKey: out_{r'} = XOR_m m * InvS(a_{r' + m}), an XOR of four bytes
+      and the key, in the +-1 domain the five-leaf product
+      ((T[r'][0e] * DK) * (T[r'+1][0b] * T[r'+2][0d])) * T[r'+3][09]: 4 products per output bit,
+      depth 3, the key joining at the S-box output level (KEY_OFFSET 4 as forward).
+    88 + 128 + 128 = 344 key switches per round and slab against 256 forward."""
+
+    def __init__(self, engine: Engine, sk, pk, rlk, cjk=None, rotation_keys=None):
+        super().__init__(engine, sk, pk, rlk, cjk, rotation_keys)
+        self.WI64 = np.rint(walsh_inv_sbox() * 64).astype(np.int32)  # (8, 16, 16)
+        self.WT64 = np.rint(walsh_inv_tbox() * 64).astype(np.int32).reshape(32, 16, 16)  # output 8 m + j
+
+    # ---- round steps --------------------------------------------------------------------------
+    def _inv_sbox_rows(self, bits, W64) -> list:
+        """One poly2_int per state row under the weights W64 ((outputs, 16, 16)), row r's outputs
+        written rotated by (4 - r) mod 4 within each slab (InvShiftRows).  A row's monomials are
+        dropped before the next row's are built."""
+        out = []
+        for r, row in enumerate(bits):
+            mh = self.monomials(row[4:8])
+            ml = self.monomials(row[0:4])
+            out.append(self.e.poly2_int([mh[i] for i in range(1, 16)], [ml[j] for j in range(1, 16)],
+                                        W64, 64, self.rlk, slab_rot=(4 - r) % 4))
+            del mh, ml
+        return out
+
+    def inv_sub_bytes_shift_rows_mix(self, bits) -> list:
+        """T[r][m][j]: bit j of INV_MIX[m] * InvS(byte) of row r after InvShiftRows -- the four
+        InvMixColumns multiples of every byte from one 32-output S-box call per row, depth 4."""
+        return [[o[8 * m:8 * m + 8] for m in range(4)] for o in self._inv_sbox_rows(bits, self.WT64)]
+
+    def inv_mix_columns_add_round_key(self, Tb, dkey) -> List[List[Ciphertext]]:
+        """out_{r',j} ^ dk_{r',j} = ((T[r'][0][j] * DK[r'][j]) * (T[r'+1][1][j] * T[r'+2][2][j]))
+        * T[r'+3][3][j]: 128 products, depth 3.  The key product comes first (the batch-4 key is
+        cycled, key_mul); of the two five-leaf trees of depth 3 this one levels down one leaf per
+        output bit (the 09 multiple, by two levels, inside the last product), the other,
+        ((a b) c) (d e), two."""
+        return [[self.mul(self.mul(self.key_mul(Tb[r][0][j], dkey[r][j]),
+                                   self.mul(Tb[(r + 1) % 4][1][j], Tb[(r + 2) % 4][2][j])),
+                          Tb[(r + 3) % 4][3][j])
+                 for j in range(8)] for r in range(4)]
+
+    def inv_sub_bytes_shift_rows(self, bits) -> List[List[Ciphertext]]:
+        """InvSubBytes with InvShiftRows folded into the output order: 8 outputs per row."""
+        return self._inv_sbox_rows(bits, self.WI64)
+
+    def round(self, bits, key, timings: dict | None = None):
+        """InvSubBytes -> InvShiftRows -> InvMixColumns -> AddRoundKey(dk): one middle round of
+        the equivalent inverse cipher (aes_tables.eq_inv_round), depth 7."""
+        import time
+        t0 = time.perf_counter()
+        Tb = self.inv_sub_bytes_shift_rows_mix(bits)
+        if timings is not None:
+            self.e.materialize(Tb)
+            self.e.synchronize()
+            t1 = time.perf_counter()
+            timings["inv_sub_bytes_shift_rows_mix"] = timings.get("inv_sub_bytes_shift_rows_mix", 0.0) + t1 - t0
+        out = self.inv_mix_columns_add_round_key(Tb, key)
+        if timings is not None:
+            self.e.materialize(out)
+            self.e.synchronize()
+            timings["inv_mix_columns_add_round_key"] = (timings.get("inv_mix_columns_add_round_key", 0.0)
+                                                        + time.perf_counter() - t1)
+        return out
+
+    def final_round(self, bits, key):
+        """InvSubBytes + InvShiftRows -> AddRoundKey (the last round: no InvMixColumns), depth 5."""
+        return self.add_round_key(self.inv_sub_bytes_shift_rows(bits), key)
+
+    # ---- whole decryptions ----------------------------------------------------------------------
+    def decrypt_aes128(self, bits, dkeys, bs, **kw):
+        """AES-128 decryption of the encrypted bit state under the 11 encrypted decryption keys
+        (at key_levels): encrypt_aes128's body under this class's rounds; arguments as there."""
+        return self.encrypt_aes128(bits, dkeys, bs, **kw)
+
+    def _check_cipher_input(self, data, dkeys, bss, want_levels, what: str):
+        """The refusals of transcipher_ecb / transcipher_cbc, before any ciphertext work."""
+        shape = tuple(getattr(data, "shape", ()))
+        if len(shape) != 3 or shape[0] < 1 or shape[1:] != (self.n_blk, 16):
+            raise ValueError(f"data must be (NB, {self.n_blk}, 16) bytes, got {shape}")
+        if len(dkeys) != 11:
+            raise ValueError(f"expected 11 decryption keys, got {len(dkeys)}")
+        have = [k[0][0].level for k in dkeys]
+        if have != want_levels:
+            raise ValueError(f"decryption keys at levels {have}; {what} needs {want_levels}")
+
+    def transcipher_ecb(self, data, dkeys, bs, out_level: int = 0, **kw):
+        """AES-128-ECB decryption of `data` ((NB, n_blk, 16) bytes) under the encrypted decryption
+        keys, which sit at key_levels(L, bs, out_level), L = dkeys[0]'s level: the +-1 bit
+        ciphertexts of the message and the number of refreshes.  State 0 = dk_0 times the data
+        planes (no encrypted input state, as counter_state), then rounds 1..10.  A wrong data
+        shape, keys at other levels and an out_level no bootstrapper can leave are ValueErrors
+        before any ciphertext work."""
+        bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
+        L = dkeys[0][0][0].level
+        want = self.key_levels(L, bss, out_level)  # ValueError: no bootstrapper leaves out_level
+        self._check_cipher_input(data, dkeys, bss, want, f"key_levels({L}, bs, out_level={out_level})")
+        S = self.mul_planes(dkeys[0], self.data_planes(data))
+        return self.rounds_1_to_10(S, dkeys, bss, out_level=out_level, **kw)
+
+    def previous_blocks(self, data, iv):
+        """The block before every block of `data` (aes_tables.cbc_previous): numpy on the oracle,
+        torch on the client device on the HIP engine (as data_planes)."""
+        iv = np.asarray(bytearray(iv) if isinstance(iv, (bytes, bytearray)) else iv)
+        if iv.shape != (16,):
+            raise ValueError(f"iv must be the 16 bytes before the first block, got shape {iv.shape}")
+        iv = iv.astype(np.uint8)
+        if not self.e.on_device:
+            if not isinstance(data, np.ndarray):
+                data = data.cpu().numpy()
+            return T.cbc_previous(data, iv)
+        import torch
+        t = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.array(data, dtype=np.uint8))
+        t = t.to(self.e.client_device)
+        flat = t.reshape(-1, 16)
+        return torch.cat([torch.from_numpy(iv).to(flat.device)[None], flat[:-1]]).reshape(t.shape)
+
+    def transcipher_cbc(self, data, iv, dkeys, bs, out_level: int = 0, **kw):
+        """AES-128-CBC decryption of `data` ((NB, n_blk, 16) bytes, blocks chained in C order)
+        under the encrypted decryption keys: message block i = D(c_i) XOR c_{i-1}, every block on
+        its own.  `iv` is the 16-byte chaining value before the first block (for a later chunk or
+        a rank's slice: the ciphertext block before its first).  The shifted ciphertext is folded
+        into the last key (fold_data_key), so the chaining XOR costs the state no level; the keys
+        sit at ctr_key_levels(L, bs, out_level).  Refusals and the result as transcipher_ecb."""
+        bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
+        L = dkeys[0][0][0].level
+        want = self.ctr_key_levels(L, bss, out_level)
+        self._check_cipher_input(data, dkeys, bss, want, f"ctr_key_levels({L}, bs, out_level={out_level})")
+        prev = self.previous_blocks(data, iv)
+        keys = list(dkeys)
+        keys[10] = self.fold_data_key(keys[10], prev)
+        S = self.mul_planes(keys[0], self.data_planes(data))
+        return self.rounds_1_to_10(S, keys, bss, out_level=out_level, **kw)

@@ -155,3 +155,122 @@ def ctr_xor(data: np.ndarray, key: bytes | np.ndarray, iv: bytes | np.ndarray, f
 def aes_round(state: np.ndarray, round_key: np.ndarray) -> np.ndarray:
     """One full middle round: SubBytes -> ShiftRows -> MixColumns -> AddRoundKey."""
     return mix_columns(shift_rows(sub_bytes(state))) ^ round_key
+
+
+# ---------------------------------------------------------------------------------------------
+# the inverse cipher (FIPS-197 5.3) and the block modes that need it
+def inv_sub_bytes(s: np.ndarray) -> np.ndarray:
+    return INV_SBOX[s]
+
+
+def decrypt_block(block: np.ndarray, key: bytes | np.ndarray) -> np.ndarray:
+    """The straight inverse cipher (FIPS-197 5.3): the encryption round keys in reverse order,
+    InvShiftRows -> InvSubBytes -> AddRoundKey -> InvMixColumns."""
+    rk = expand_key(key)
+    s = np.asarray(block, dtype=np.uint8) ^ rk[10]
+    for r in range(9, 0, -1):
+        s = inv_mix_columns(inv_sub_bytes(inv_shift_rows(s)) ^ rk[r])
+    return inv_sub_bytes(inv_shift_rows(s)) ^ rk[0]
+
+
+def decryption_keys(key: bytes | np.ndarray) -> np.ndarray:
+    """(11, 16) round keys of the equivalent inverse cipher (FIPS-197 5.3.5): dk[0] = k_10,
+    dk[i] = InvMixColumns(k_{10-i}) for i = 1..9, dk[10] = k_0."""
+    rk = expand_key(key)
+    dk = rk[::-1].copy()
+    dk[1:10] = inv_mix_columns(dk[1:10])
+    return dk
+
+
+def eq_inv_round(state: np.ndarray, dk: np.ndarray) -> np.ndarray:
+    """One middle round of the equivalent inverse cipher: InvSubBytes -> InvShiftRows ->
+    InvMixColumns -> AddRoundKey(dk), dk a row of decryption_keys."""
+    return inv_mix_columns(inv_shift_rows(inv_sub_bytes(state))) ^ dk
+
+
+def eq_decrypt_block(block: np.ndarray, dk: np.ndarray) -> np.ndarray:
+    """The equivalent inverse cipher under dk = decryption_keys(key): the structure of
+    encrypt_block (an initial AddRoundKey, nine middle rounds, a last one without the mixing)."""
+    s = np.asarray(block, dtype=np.uint8) ^ dk[0]
+    for r in range(1, 10):
+        s = eq_inv_round(s, dk[r])
+    return inv_shift_rows(inv_sub_bytes(s)) ^ dk[10]
+
+
+def ecb_encrypt(data: np.ndarray, key: bytes | np.ndarray) -> np.ndarray:
+    return encrypt_block(np.asarray(data, dtype=np.uint8), key)
+
+
+def ecb_decrypt(data: np.ndarray, key: bytes | np.ndarray) -> np.ndarray:
+    return decrypt_block(np.asarray(data, dtype=np.uint8), key)
+
+
+def _iv16(iv) -> np.ndarray:
+    iv = np.asarray(bytearray(iv) if isinstance(iv, (bytes, bytearray)) else iv, dtype=np.uint8)
+    if iv.shape != (16,):
+        raise ValueError("the initialisation vector has 16 bytes")
+    return iv
+
+
+def cbc_previous(data: np.ndarray, iv: bytes | np.ndarray) -> np.ndarray:
+    """The block before every block of `data` ((..., 16) bytes, blocks counted in C order): the
+    ciphertext shifted by one block, `iv` before the first."""
+    d = np.asarray(data, dtype=np.uint8)
+    flat = d.reshape(-1, 16)
+    return np.concatenate([_iv16(iv)[None], flat[:-1]]).reshape(d.shape)
+
+
+def _encrypt_chain(blocks: list, rk: list, prev: int) -> list:
+    """CBC's sequential chain on Python integers (a block = one 128-bit big-endian integer, byte i
+    at bits 8 (15 - i)): c_i = E(p_i ^ c_{i-1}).  One round = 16 lookups in a table per byte
+    position, each entry the byte's SubBytes -> ShiftRows -> MixColumns contribution to the block
+    (built from SBOX, GF2 and GF3 here: the numpy round functions, one block at a time, are
+    ~50 times slower, and the chain cannot be batched)."""
+    def place(col):  # 4 bytes of a column (row 0 first) at byte index r + 4c of the block
+        return lambda c: sum(int(b) << (8 * (15 - (r + 4 * c))) for r, b in enumerate(col))
+    mid, last = [], []
+    for i in range(16):
+        r, c = i % 4, ((i // 4) - (i % 4)) % 4  # byte (r, c') lands in column c = c' - r
+        mt, lt = [], []
+        for x in range(256):
+            s = int(SBOX[x])
+            col = [0, 0, 0, 0]  # MixColumns of a column holding s in row r
+            col[r], col[(r - 1) % 4], col[(r - 2) % 4], col[(r - 3) % 4] = int(GF2[s]), int(GF3[s]), s, s
+            mt.append(place(col)(c))
+            lt.append(s << (8 * (15 - (r + 4 * c))))
+        mid.append(mt)
+        last.append(lt)
+    shifts = [8 * (15 - i) for i in range(16)]
+    out = []
+    for p in blocks:
+        s = p ^ prev ^ rk[0]
+        for rnd in range(1, 10):
+            t = rk[rnd]
+            for i in range(16):
+                t ^= mid[i][(s >> shifts[i]) & 0xFF]
+            s = t
+        t = rk[10]
+        for i in range(16):
+            t ^= last[i][(s >> shifts[i]) & 0xFF]
+        out.append(t)
+        prev = t
+    return out
+
+
+def cbc_encrypt(data: np.ndarray, key: bytes | np.ndarray, iv: bytes | np.ndarray) -> np.ndarray:
+    """AES-128-CBC encryption of (..., 16) bytes, blocks chained in C order (sequential)."""
+    d = np.asarray(data, dtype=np.uint8)
+    flat = np.ascontiguousarray(d).reshape(-1, 16)
+    rk = [int.from_bytes(bytes(k), "big") for k in expand_key(key)]
+    raw = flat.tobytes()
+    blocks = [int.from_bytes(raw[i:i + 16], "big") for i in range(0, len(raw), 16)]
+    enc = _encrypt_chain(blocks, rk, int.from_bytes(bytes(_iv16(iv)), "big"))
+    out = np.frombuffer(b"".join(c.to_bytes(16, "big") for c in enc), dtype=np.uint8)
+    return out.reshape(d.shape).copy()
+
+
+def cbc_decrypt(data: np.ndarray, key: bytes | np.ndarray, iv: bytes | np.ndarray) -> np.ndarray:
+    """AES-128-CBC decryption: block i is decrypt_block(c_i) XOR c_{i-1}, c_{-1} = iv -- every
+    block on its own (a later chunk takes the block before its first as `iv`)."""
+    d = np.asarray(data, dtype=np.uint8)
+    return decrypt_block(d, key) ^ cbc_previous(d, iv)
