@@ -78,6 +78,31 @@ def _keys(eng):
                 hoist=[eng.create_hoisted_rotation_key(sk, d) for d in (-1, 5)[:NHOIST]])
 
 
+def _key_residues(eng, key):
+    """aesfhe_key_export of a switching key: (kind, galois element, (digits, 2: b then a,
+    L + 1 + K, N) NTT-form residues)."""
+    kind, g, seed, words = C.c_int32(), C.c_uint64(), C.c_uint64(), C.c_int64()
+    eng._check(eng._lib.key_export(eng._h, key._h, C.byref(kind), C.byref(g), C.byref(seed), C.byref(words), None))
+    data = np.empty(words.value, dtype=np.uint64)
+    eng._check(eng._lib.key_export(eng._h, key._h, C.byref(kind), C.byref(g), C.byref(seed), C.byref(words),
+                                   data.ctypes.data_as(C.POINTER(C.c_uint64))))
+    n, np_ = 1 << eng.log_coeff_count, len(eng.primes)
+    assert kind.value in (2, 3, 5) and words.value % (2 * np_ * n) == 0
+    return kind.value, g.value, data.reshape(-1, 2, np_, n)
+
+
+def _key_from_residues(eng, cls, kind, arr, galois=0):
+    """aesfhe_key_import of a switching key given residue by residue (_key_residues' layout)."""
+    a = np.ascontiguousarray(arr, dtype=np.uint64)
+    out = C.c_void_p()
+    eng._check(eng._lib.key_import(eng._h, kind, galois, 0, a.ctypes.data_as(C.POINTER(C.c_uint64)), a.size,
+                                   C.byref(out)))
+    k = eng._key(cls, out.value)
+    if kind != 2:
+        k.galois_elt = galois
+    return k
+
+
 def _pool(primes, L, B, npoly, seed, n=N16):
     """Uniformly random residues (B, npoly, L + 1, n): limb i below primes[i], so that the first
     l + 1 limbs are a valid ciphertext at any level l."""
