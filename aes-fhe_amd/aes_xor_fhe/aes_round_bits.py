@@ -43,6 +43,7 @@ schedule and the refreshes above apply unchanged.
 """
 from __future__ import annotations
 
+import time
 from typing import Dict, List, Sequence
 
 import numpy as np
@@ -54,22 +55,12 @@ XT_OF = {0: (7, False), 1: (0, True), 2: (1, False), 3: (2, True), 4: (3, True),
          6: (5, False), 7: (6, False)}  # xtime bit j = u[src] (* u[7] if flagged)
 
 
-def walsh_sbox() -> np.ndarray:
-    """W[t, S, T]: +-1 S-box output bit t as sum_{S,T} W M^hi_S M^lo_T (S, T = 4-bit masks of
-    the high / low nibble bits; mask 0 = the constant monomial)."""
-    x = np.arange(256)
-    f = np.stack([1.0 - 2.0 * ((T.SBOX[x].astype(np.int64) >> t) & 1) for t in range(8)])
-    mono = np.array([[np.prod([1 - 2 * ((v >> k) & 1) for k in range(4) if (m >> k) & 1])
-                      for v in range(16)] for m in range(16)], dtype=np.float64)  # [mask, nibble]
-    hi, lo = x >> 4, x & 15
-    return np.einsum("tx,sx,ux->tsu", f, mono[:, hi], mono[:, lo]) / 256.0
-
-
 INV_MIX = (14, 11, 13, 9)  # InvMixColumns: out_r' = XOR_r INV_MIX[(r - r') mod 4] * a_r
 
 
 def _walsh_bytes(table: np.ndarray) -> np.ndarray:
-    """walsh_sbox for any byte function `table` (256 bytes): W[t, S, T] of its +-1 output bit t."""
+    """W[t, S, T] of a byte function `table` (256 bytes): its +-1 output bit t as sum_{S,T} W M^hi_S
+    M^lo_T (S, T = 4-bit masks of the high / low nibble bits; mask 0 = the constant monomial)."""
     x = np.arange(256)
     f = np.stack([1.0 - 2.0 * ((np.asarray(table)[x].astype(np.int64) >> t) & 1) for t in range(8)])
     mono = np.array([[np.prod([1 - 2 * ((v >> k) & 1) for k in range(4) if (m >> k) & 1])
@@ -78,6 +69,11 @@ def _walsh_bytes(table: np.ndarray) -> np.ndarray:
     W = np.einsum("tx,sx,ux->tsu", f, mono[:, hi], mono[:, lo]) / 256.0
     assert np.array_equal(np.rint(W * 64) / 64.0, W)  # 64 W is an integer
     return W
+
+
+def walsh_sbox() -> np.ndarray:
+    """W[t, S, T] of the S-box: (8, 16, 16)."""
+    return _walsh_bytes(T.SBOX)
 
 
 def walsh_inv_sbox() -> np.ndarray:
@@ -93,11 +89,62 @@ def walsh_inv_tbox() -> np.ndarray:
     return np.stack([_walsh_bytes(T.GF_MUL_TABLES[c][T.INV_SBOX]) for c in INV_MIX])
 
 
+def _as_list(bs) -> list:
+    """One bootstrapper or a list of them (cheapest first) -> the list."""
+    return list(bs) if isinstance(bs, (list, tuple)) else [bs]
+
+
+class _Levels:
+    """The round loop's state as a level alone (AESRowRound.run_rounds: what schedule plans on)."""
+    def __init__(self, R, level: int):
+        self.R, self.level = R, level
+
+    def refresh(self, rnd, b, clean):
+        self.level = b.bits_level
+
+    def round(self, rnd, final):
+        self.level -= self.R.FINAL_DEPTH if final else self.R.ROUND_DEPTH
+
+
+class _Bits:
+    """The round loop's state as ciphertexts: S under keys[1..ROUNDS].  Its level is the live one,
+    so keys that sit below key_levels pull the loop along."""
+    def __init__(self, R, S, keys, timings, pairs_per_call, progress, probe):  # cipher_rounds' arguments
+        self.R, self.S, self.keys, self.timings = R, S, keys, timings
+        self.pairs_per_call, self.progress, self.probe, self.refreshes = pairs_per_call, progress, probe, 0
+
+    @property
+    def level(self) -> int:
+        return min(c.level for row in self.S for c in row)
+
+    def refresh(self, rnd, b, clean):
+        t0, scale = time.perf_counter(), 2.0 if clean else 1.0  # clean_bits leaves 2 * (+-1)
+        S = self.R.clean_bits(self.S) if clean else self.S
+        if self.probe is not None:
+            self.probe(rnd, S, scale)
+        self.S = self.R.refresh(S, b, self.pairs_per_call, in_scale=scale)
+        self.refreshes += 1
+        if self.progress:
+            self.progress(f"refresh {self.refreshes} before round {rnd} (CtS in {b.cts_groups} maps, output level "
+                          f"{b.bits_level}{', bits cleaned first' if clean else ''})")
+        self.R._mark(self.timings, "bootstrap", t0, self.S)
+
+    def round(self, rnd, final):
+        t0, lvl = time.perf_counter(), self.level
+        self.S = self.R.final_round(self.S, self.keys[rnd]) if final else self.R.round(self.S, self.keys[rnd])
+        if self.progress:
+            self.progress(f"round {rnd} from level {lvl}")
+        t1 = self.R._mark(self.timings, "rounds", t0, self.S)  # deferred products belong to this round's time
+        if self.timings is not None:
+            self.timings.setdefault("per_round", []).append((rnd, lvl, round(1e3 * (t1 - t0), 1)))
+
+
 class AESRowRound:
     """State: 4 rows x 8 +-1 bit ciphertexts (row r, bit j), each batched over NB sets of
     n_blk blocks."""
 
     GRANULE = 1  # batch elements a shard across ranks must keep together (parallel.shard_range)
+    ROUNDS = T.ROUNDS  # the loop runs rounds 1..ROUNDS under ROUNDS + 1 keys, the last without MixColumns
 
     def __init__(self, engine: Engine, sk, pk, rlk, cjk=None, rotation_keys=None):
         self.e = engine
@@ -254,7 +301,7 @@ class AESRowRound:
     ROUND_DEPTH, FINAL_DEPTH = 7, 5
 
     def final_round(self, bits, key):
-        """SubBytes -> ShiftRows -> AddRoundKey (AES round 10: no MixColumns), depth 5."""
+        """SubBytes -> ShiftRows -> AddRoundKey (the last AES round: no MixColumns), depth 5."""
         return self.add_round_key(self.shift_rows(self.sub_bytes(bits)), key)
 
     def refresh(self, bits, bs, pairs_per_call: int = 8, in_scale: float = 1.0):
@@ -317,14 +364,13 @@ class AESRowRound:
 
     def refreshes_after(self, rnd: int, level: int, top: int, stc: int, with_clean: bool = False,
                         out_level: int = 0):
-        """Refreshes that rounds rnd..10 need when they start right after a refresh at `level`,
-        later refreshes returning `top` (inf if a round would run out of levels, or round 10 end
+        """Refreshes that rounds rnd..ROUNDS need when they start right after a refresh at `level`,
+        later refreshes returning `top` (inf if a round would run out of levels, or the last end
         below `out_level`).  with_clean: (that count, 1 if the last of those refreshes cannot be
-        preceded by clean_bits else 0)."""
-        n, since, lvl = 0, 0, level
-        last_clean = True
-        for r in range(rnd, 11):
-            final = r == 10
+        preceded by clean_bits else 0).  run_rounds' look-ahead, which picks no bootstrapper."""
+        n, since, lvl, last_clean = 0, 0, level, True
+        for r in range(rnd, self.ROUNDS + 1):
+            final = r == self.ROUNDS
             if self.needs_refresh(lvl, final, since, True, stc, out_level):
                 if since == 0:
                     return (float("inf"), 1) if with_clean else float("inf")
@@ -338,7 +384,7 @@ class AESRowRound:
 
     def pick_bootstrapper(self, bss, rnd: int, out_level: int = 0):
         """The first of `bss` (cheapest first) whose output level keeps the fewest refreshes for
-        rounds rnd..10: a refresh followed by two middle rounds and another refresh needs only
+        rounds rnd..ROUNDS: a refresh followed by two middle rounds and another refresh needs only
         2 * 7 + StC levels, the one before the last three rounds 7 + 7 + 5 (+ out_level)."""
         if len(bss) == 1:
             return bss[0]
@@ -351,19 +397,30 @@ class AESRowRound:
     def refresh_step(self, S, rnd: int, level: int, since: int, refreshed: bool, bss, pairs_per_call: int,
                      probe=None, out_level: int = 0):
         """The refresh before round rnd (state S at `level`, `since` rounds after the previous
-        refresh): pick the bootstrapper, clean the bits first when this is the last refresh and
-        can_clean allows it, bootstrap.  Returns (state, bootstrapper, cleaned).  probe: optional
-        callable(rnd, state, in_scale) shown the state the bootstrap takes (after the cleaning)."""
-        stc = len(bss[0].stc_bits)
+        one) outside the round loop: _refresh_choice, then _Bits.refresh.  Returns (state, bootstrapper,
+        cleaned).  probe: optional callable(rnd, state, in_scale) shown the bootstrap's input."""
+        b, clean = self._refresh_choice(rnd, level, since, refreshed, bss, out_level)
+        st = _Bits(self, S, None, None, pairs_per_call, None, probe)
+        st.refresh(rnd, b, clean)
+        return st.S, b, clean
+
+    def _refresh_choice(self, rnd: int, level: int, since: int, refreshed: bool, bss, out_level: int = 0):
+        """(pick_bootstrapper's choice, clean first?): cleaned when it is the last refresh and can_clean allows."""
+        stc, top = len(bss[0].stc_bits), max(x.bits_level for x in bss)
         b = self.pick_bootstrapper(bss, rnd, out_level)
-        top = max(x.bits_level for x in bss)
-        clean = (self.can_clean(level, since, refreshed, stc)
-                 and self.refreshes_after(rnd, b.bits_level, top, stc, out_level=out_level) == 0)
-        if clean:
-            S = self.clean_bits(S)
-        if probe is not None:
-            probe(rnd, S, 2.0 if clean else 1.0)
-        return self.refresh(S, b, pairs_per_call, in_scale=2.0 if clean else 1.0), b, clean
+        return b, (self.can_clean(level, since, refreshed, stc)
+                   and self.refreshes_after(rnd, b.bits_level, top, stc, out_level=out_level) == 0)
+
+    def _mark(self, timings: dict | None, name: str, t0: float, obj=None) -> float:
+        """Add the time since t0 to timings[name], `obj`'s deferred products included (they belong
+        to the stage that made them); returns the time now.  timings None: nothing is run or timed."""
+        if timings is None:
+            return t0
+        self.e.materialize(obj)
+        self.e.synchronize()
+        t1 = time.perf_counter()
+        timings[name] = timings.get(name, 0.0) + (t1 - t0)
+        return t1
 
     def bit_margin(self, bits, scale: float = 1.0) -> float:
         """max over every slot of every bit ciphertext of | |v| / scale - 1 |: how far the +-1 bit
@@ -398,33 +455,36 @@ class AESRowRound:
     def schedule(self, L: int, bss, out_level: int = 0):
         """[(round, input level, bootstrapper refreshing before it or None)] that encrypt_aes128
         runs from a fresh encryption at level L (ARK0 -> L - 1); bss as there (objects with
-        bits_level / stc_bits suffice).  out_level: the level round 10 must end at or above (0:
-        the schedule that lands on level 0).  A positive out_level that the bootstrappers cannot
-        satisfy -- a round whose depth does not fit, a refresh without its SlotToCoeff levels, an
-        end below out_level -- is a ValueError."""
-        bss = list(bss) if isinstance(bss, (list, tuple)) else [bss]
-        return self._plan(L - 1, bss, out_level)
+        bits_level / stc_bits suffice).  out_level: the level the last round must end at or above
+        (0: the schedule that lands on level 0).  A positive out_level that the bootstrappers
+        cannot satisfy -- a round whose depth does not fit, a refresh without its SlotToCoeff
+        levels, an end below out_level -- is a ValueError."""
+        return self.run_rounds(_Levels(self, L - 1), _as_list(bss), out_level)
 
-    def _plan(self, lvl: int, bss, out_level: int = 0):
-        """schedule from the state AddRoundKey(k_0) leaves at level `lvl` (bss a list)."""
+    def run_rounds(self, st, bss, out_level: int = 0):
+        """Rounds 1..ROUNDS with their refreshes on the state `st` that AddRoundKey(k_0) left
+        (_Levels: the plan alone; _Bits: the ciphertexts), bss a list: the one place that decides
+        where to refresh, with which bootstrapper and whether to clean first, from st.level as it
+        is then (a live run follows ciphertexts that sit below the plan).  Returns schedule's list."""
         stc = len(bss[0].stc_bits)
+        assert all(len(b.stc_bits) == stc for b in bss)
         out, since, nref = [], 0, 0
-        for rnd in range(1, 11):
-            final = rnd == 10
+        for rnd in range(1, self.ROUNDS + 1):
+            final, b, lvl = rnd == self.ROUNDS, None, st.level
             need = self.FINAL_DEPTH if final else self.ROUND_DEPTH
-            b = None
             if self.needs_refresh(lvl, final, since, nref > 0, stc, out_level):
-                b = self.pick_bootstrapper(bss, rnd, out_level)
+                b, clean = self._refresh_choice(rnd, lvl, since, nref > 0, bss, out_level)
                 if out_level and lvl < stc:
                     raise ValueError(f"out_level {out_level}: the refresh before round {rnd} would start at level "
                                      f"{lvl}, below SlotToCoeff's {stc}")
-                lvl, since, nref = b.bits_level, 0, nref + 1
+                st.refresh(rnd, b, clean)
+                lvl, since, nref = st.level, 0, nref + 1
             if out_level and lvl - need < (out_level if final else 0):
                 raise ValueError(f"out_level {out_level}: round {rnd} from level {lvl} ends below "
                                  f"{out_level if final else 0} (the bootstrappers return level "
                                  f"{max(x.bits_level for x in bss)} at most)")
             out.append((rnd, lvl, b))
-            lvl -= need
+            st.round(rnd, final)
             since += 1
         return out
 
@@ -461,76 +521,34 @@ class AESRowRound:
         through that list.  probe: optional callable(rnd, state, in_scale) shown every refresh's
         input (refresh_step).  out_level: the level the result must keep (schedule; ValueError
         before any ciphertext work if the bootstrappers cannot leave it)."""
-        bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
         if out_level:
-            self._plan(min(min(c.level for row in bits for c in row), keys[0][0][0].level) - 1, bss, out_level)
+            self.schedule(min(min(c.level for row in bits for c in row), keys[0][0][0].level), bs, out_level)
         S = self.add_round_key(bits, keys[0])
         if consume:
             self.e.materialize(S)
             for row in bits:
                 row.clear()
-        return self.rounds_1_to_10(S, keys, bss, timings, pairs_per_call, progress, probe, out_level)
+        return self.cipher_rounds(S, keys, bs, timings, pairs_per_call, progress, probe, out_level)
 
-    def rounds_1_to_10(self, S, keys, bss, timings: dict | None = None, pairs_per_call: int = 8,
-                       progress=None, probe=None, out_level: int = 0):
-        """Rounds 1..10 with their refreshes on the state S = AddRoundKey(k_0) output, under
-        keys[1..10]: what encrypt_aes128 and AESSlicedRound.keystream_aes128 share (arguments as
-        there, bss a list).  Returns the state and the number of refreshes."""
-        import time
-        stc = len(bss[0].stc_bits)
-        assert all(len(b.stc_bits) == stc for b in bss)
-        if out_level:
-            self._plan(min(c.level for row in S for c in row), bss, out_level)
-        refreshes = 0
-        since = 0
-        for rnd in range(1, 11):
-            final = rnd == 10
-            lvl = min(c.level for row in S for c in row)
-            if self.needs_refresh(lvl, final, since, refreshes > 0, stc, out_level):
-                t0 = time.perf_counter()
-                S, b, clean = self.refresh_step(S, rnd, lvl, since, refreshes > 0, bss, pairs_per_call, probe, out_level)
-                since = 0
-                refreshes += 1
-                if progress:
-                    progress(f"refresh {refreshes} before round {rnd} (CtS in {b.cts_groups} maps, output level "
-                             f"{b.bits_level}{', bits cleaned first' if clean else ''})")
-                if timings is not None:
-                    self.e.materialize(S)
-                    self.e.synchronize()
-                    timings["bootstrap"] = timings.get("bootstrap", 0.0) + time.perf_counter() - t0
-            t0 = time.perf_counter()
-            lvl = min(c.level for row in S for c in row)
-            S = self.final_round(S, keys[rnd]) if final else self.round(S, keys[rnd])
-            since += 1
-            if progress:
-                progress(f"round {rnd} from level {lvl}")
-            if timings is not None:
-                self.e.materialize(S)  # deferred products belong to this round's time
-                self.e.synchronize()
-                dt = time.perf_counter() - t0
-                timings["rounds"] = timings.get("rounds", 0.0) + dt
-                timings.setdefault("per_round", []).append((rnd, lvl, round(1e3 * dt, 1)))
-        return S, refreshes
+    def cipher_rounds(self, S, keys, bs, timings: dict | None = None, pairs_per_call: int = 8,
+                      progress=None, probe=None, out_level: int = 0):
+        """run_rounds on the ciphertexts S = AddRoundKey(k_0) output under keys[1..ROUNDS], for
+        encrypt_aes128, keystream_aes128, transcipher_ecb and _cbc: (state, number of refreshes)."""
+        bss, st = _as_list(bs), _Bits(self, S, keys, timings, pairs_per_call, progress, probe)
+        if out_level:  # the ValueError comes before any ciphertext work
+            self.run_rounds(_Levels(self, st.level), bss, out_level)
+        self.run_rounds(st, bss, out_level)
+        return st.S, st.refreshes
 
     def round(self, bits, key, timings: dict | None = None):
         """SubBytes -> ShiftRows -> MixColumns -> AddRoundKey on the row-sliced +-1 bit state."""
-        import time
-
-        def mark(name, t0, obj=None):
-            if timings is None:
-                return t0
-            self.e.materialize(obj)  # deferred products belong to this stage
-            self.e.synchronize()
-            t1 = time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + (t1 - t0)
-            return t1
-        t = mark("start", 0.0) if timings is not None else 0.0
+        t = self._mark(timings, "start", 0.0)
         A = self.sub_bytes(bits)  # SubBytes first: ShiftRows commutes with it and is cheaper
-        t = mark("sub_bytes", t, A)  # on the SubBytes output (level l-4: fewer limbs per rotation)
+        t = self._mark(timings, "sub_bytes", t, A)  # on the SubBytes output (level l-4: fewer limbs per rotation)
         A = self.shift_rows(A)
-        t = mark("shift_rows", t, A)
+        t = self._mark(timings, "shift_rows", t, A)
         out = self.mix_columns_add_round_key(A, key)
-        mark("mix_columns_add_round_key", t, out)
+        self._mark(timings, "mix_columns_add_round_key", t, out)
         return out
 
 
@@ -626,12 +644,13 @@ class AESSlicedRound(AESRowRound):
         rows = [np.repeat(rk[[r + 4 * c for c in range(4)]], self.sc).reshape(4, self.sc) for r in range(4)]
         return self.encrypt_bytes_rows(rows, level=level)
 
-    # ---- the key bundle: 11 round keys in one ciphertext -----------------
+    # ---- the key bundle: the ROUNDS + 1 round keys in one ciphertext -------
     # Every ciphertext of encrypt_round_key holds a constant polynomial (the same +-1 in every slot:
     # only coefficient 0 is non-zero), so all 11 x 4 x 8 x 4 = 1408 of them fit in the coefficients
     # of one ciphertext, which the server unpacks with Engine.expand.
-    BUNDLE_COEFFS = 2048  # 128 (row, bit, column) positions x 16 key slots (11 used)
-    BUNDLE_STAGE2 = 7  # expansion steps 4..10, run per key
+    BUNDLE_COEFFS = 2048  # 128 (row, bit, column) positions x 16 key slots: a bundle holds up to 16 keys
+    BUNDLE_STAGE2 = 7  # the expansion steps after the first 4 (which separate the keys), run per key
+    BUNDLE_STEPS = 4 + BUNDLE_STAGE2  # log2(BUNDLE_COEFFS): one expansion (galois) key per step
     BUNDLE_GAIN_BITS = 10  # the bundle's bits sit 2^10 / 2^7 above Delta: the fresh noise counts 2^-10
 
     @staticmethod
@@ -653,17 +672,17 @@ class AESSlicedRound(AESRowRound):
         return int(round(self.e.scales[level] * 2.0 ** (self.BUNDLE_GAIN_BITS - self.BUNDLE_STAGE2)))
 
     def pack_round_keys(self, rks, level: int | None = None) -> np.ndarray:
-        """11 round keys (11, 16) bytes -> the (1, N) int64 coefficients of a bundle encrypted at
+        """The 11 round keys, (ROUNDS + 1, 16) bytes -> the (1, N) int64 coefficients of a bundle encrypted at
         `level` (one above the highest key level): coefficient bundle_index(k, r, j, c) =
         (-1)^bit * bundle_amplitude(level), bit = bit j of byte r + 4c of key k."""
         n = self._bundle_ring()
         level = self.e.max_level if level is None else int(level)
         rk = np.asarray(rks, dtype=np.int64)
-        if rk.shape != (11, 16):
-            raise ValueError(f"expected 11 round keys of 16 bytes, got {rk.shape}")
+        if rk.shape != (self.ROUNDS + 1, 16):
+            raise ValueError(f"expected {self.ROUNDS + 1} round keys of 16 bytes, got {rk.shape}")
         amp = self.bundle_amplitude(level)
         co = np.zeros((1, n), dtype=np.int64)
-        k = np.arange(11)
+        k = np.arange(self.ROUNDS + 1)
         for r in range(4):
             for j in range(8):
                 for c in range(4):
@@ -677,9 +696,9 @@ class AESSlicedRound(AESRowRound):
         return self.e.encrypt_coefficients(self.pack_round_keys(rks, level), self.pk, level)
 
     def create_key_expansion_keys(self) -> list:
-        """The 11 galois keys (g = N / 2^j + 1, j = 0..10) expand_round_keys switches with."""
+        """The BUNDLE_STEPS galois keys (g = N / 2^j + 1, j = 0..10) expand_round_keys switches with."""
         self._bundle_ring()
-        return self.e.create_expansion_keys(self.sk, 0, 11)
+        return self.e.create_expansion_keys(self.sk, 0, self.BUNDLE_STEPS)
 
     def _times(self, ct: Ciphertext, m: int) -> Ciphertext:
         """ct times the integer m, exactly and without a level (Engine.lincomb_int: one launch on
@@ -715,17 +734,17 @@ class AESSlicedRound(AESRowRound):
     def expand_round_keys(self, bundle: Ciphertext, xkeys, levels) -> list:
         """The bundle -> keys[k][r][j], batch 4, key k at levels[k]: the structure of
         [encrypt_round_key(rk_k, levels[k]) for k]; keystream_aes128 / transcipher take it
-        unchanged.  Steps 0..3 give 16 elements, element k the coefficients of key k; elements
-        11..15 are dropped.  Each key's 128 elements are then expanded one level above that key's
+        unchanged.  Steps 0..3 give 16 elements, element k the coefficients of key k; those past
+        key ROUNDS are dropped.  Each key's 128 elements are then expanded one level above that key's
         own (expand_key_subtree), so that the peak is 128 elements at that key's limbs plus one."""
         self._bundle_ring()
-        if len(xkeys) != 11 or len(levels) != 11:
-            raise ValueError("expand_round_keys takes 11 expansion keys and 11 levels")
+        if len(xkeys) != self.BUNDLE_STEPS or len(levels) != self.ROUNDS + 1:
+            raise ValueError(f"expand_round_keys takes {self.BUNDLE_STEPS} expansion keys and {self.ROUNDS + 1} levels")
         if bundle.batch != 1 or max(levels) >= bundle.level:
             raise ValueError(f"the bundle must be one ciphertext at level > {max(levels)}, one above the highest key")
         by_key = self.e.expand(bundle, xkeys[:4], first=0)
         keys = []
-        for k in range(11):
+        for k in range(self.ROUNDS + 1):
             x = self.expand_key_subtree(self.e.slice(by_key, k, 1), xkeys, int(levels[k]), bundle.level)
             keys.append([[self.e.slice(x, 4 * (r * 8 + j), 4) for j in range(8)] for r in range(4)])
         return keys
@@ -753,19 +772,11 @@ class AESSlicedRound(AESRowRound):
 
     def round(self, bits, key, timings: dict | None = None):
         """SubBytes + ShiftRows (one step, sub_bytes_shift_rows) -> MixColumns -> AddRoundKey."""
-        import time
-        t0 = time.perf_counter()
+        t = time.perf_counter()
         A = self.sub_bytes_shift_rows(bits)
-        if timings is not None:
-            self.e.materialize(A)
-            self.e.synchronize()
-            t1 = time.perf_counter()
-            timings["sub_bytes_shift_rows"] = timings.get("sub_bytes_shift_rows", 0.0) + t1 - t0
+        t = self._mark(timings, "sub_bytes_shift_rows", t, A)
         out = self.mix_columns_add_round_key(A, key)
-        if timings is not None:
-            self.e.materialize(out)
-            self.e.synchronize()
-            timings["mix_columns_add_round_key"] = timings.get("mix_columns_add_round_key", 0.0) + time.perf_counter() - t1
+        self._mark(timings, "mix_columns_add_round_key", t, out)
         return out
 
     def final_round(self, bits, key):
@@ -864,27 +875,26 @@ class AESSlicedRound(AESRowRound):
         """AES-128 of the counter blocks first, first + 1, ... of `iv` (aes_tables.ctr_blocks) for
         `nb` sets of n_blk blocks under the encrypted round keys: the CTR keystream as +-1 bit
         ciphertexts, with no encrypted input state.  State 0 is counter_state(keys[0], ...) --
-        one level below keys[0], where schedule() puts AddRoundKey(k_0) -- then rounds 1..10 as
-        in encrypt_aes128 (rounds_1_to_10).  With `data` ((nb, n_blk, 16) bytes) the result is
-        keystream XOR data (fold_data_key into keys[10], which must then sit one level above the
-        one round 10 consumes: ctr_key_levels).  `first` lets a rank derive the counters of its
+        one level below keys[0], where schedule() puts AddRoundKey(k_0) -- then the rounds as in
+        encrypt_aes128 (cipher_rounds).  With `data` ((nb, n_blk, 16) bytes) the result is
+        keystream XOR data (fold_data_key into the last key, which must then sit one level above
+        the one the last round consumes: ctr_key_levels).  `first` lets a rank derive the counters of its
         own slab range.  out_level: the level the result must keep (schedule; the keys then sit at
         key_levels / ctr_key_levels of the same out_level).  Returns the state and the number of
         refreshes."""
-        bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
-        keys = list(keys)
+        keys, last = list(keys), self.ROUNDS
         if out_level:
-            self.schedule(keys[0][0][0].level, bss, out_level)  # ValueError before any ciphertext work
+            self.schedule(keys[0][0][0].level, bs, out_level)  # ValueError before any ciphertext work
         if data is not None:
             if tuple(data.shape) != (nb, self.n_blk, 16):
                 raise ValueError(f"data must be ({nb}, {self.n_blk}, 16) bytes, got {tuple(data.shape)}")
-            want = self.ctr_key_levels(keys[0][0][0].level, bss, out_level)[10]
-            if keys[10][0][0].level < want:
-                raise ValueError(f"keys[10] is at level {keys[10][0][0].level}; folding data into it needs "
+            want = self.ctr_key_levels(keys[0][0][0].level, bs, out_level)[last]
+            if keys[last][0][0].level < want:
+                raise ValueError(f"keys[{last}] is at level {keys[last][0][0].level}; folding data into it needs "
                                  f"level {want} (ctr_key_levels)")
-            keys[10] = self.fold_data_key(keys[10], data)
+            keys[last] = self.fold_data_key(keys[last], data)
         S = self.counter_state(keys[0], iv, nb, first)
-        return self.rounds_1_to_10(S, keys, bss, timings, pairs_per_call, progress, probe, out_level)
+        return self.cipher_rounds(S, keys, bs, timings, pairs_per_call, progress, probe, out_level)
 
     def transcipher(self, data, iv, keys, bs, first: int = 0, out_level: int = 0, **kw):
         """AES-128-CTR decryption of `data` ((NB, n_blk, 16) bytes encrypted from counter `first`
@@ -992,23 +1002,22 @@ class AESSlicedRound(AESRowRound):
         2).  The keys must sit at ctr_key_levels(L, bs, out_level=t), L = keys[0]'s level.  A
         width whose values do not fit level keep_levels (values_from_bits) and keys at other
         levels are ValueErrors before any ciphertext work."""
-        bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
         self._value_groups(width, byteorder)
         t = (self.CLEAN_LEVELS if clean else 0) + int(keep_levels)
         L = keys[0][0][0].level
-        want = self.ctr_key_levels(L, bss, out_level=t)  # ValueError if no bootstrapper leaves t levels
+        want = self.ctr_key_levels(L, bs, out_level=t)  # ValueError if no bootstrapper leaves t levels
         have = [k[0][0].level for k in keys]
         if have != want:
             raise ValueError(f"keys at levels {have}; a tail of {t} levels needs {want} "
                              f"(ctr_key_levels(L, bs, out_level={t}))")
-        end = self.schedule(L, bss, t)[-1][1] - self.FINAL_DEPTH - (self.CLEAN_LEVELS if clean else 0)
+        end = self.schedule(L, bs, t)[-1][1] - self.FINAL_DEPTH - (self.CLEAN_LEVELS if clean else 0)
         amp = 2.0 if clean else 1.0
         Q = 1
         for q in self.e.primes[:end + 1]:
             Q *= int(q)
         if 2.0 * amp * 2.0 ** width * self.e.scales[end] >= Q / 2:
             raise ValueError(f"{width}-bit values do not fit level {end}: raise keep_levels")
-        bits, refreshes = self.transcipher(data, iv, keys, bss, first=first, out_level=t, **kw)
+        bits, refreshes = self.transcipher(data, iv, keys, bs, first=first, out_level=t, **kw)
         if clean:
             bits = self.clean_bits(bits)
         cts, amplitude = self.values_from_bits(bits, width, byteorder, in_scale=amp)
@@ -1078,20 +1087,11 @@ class AESSlicedDecrypt(AESSlicedRound):
     def round(self, bits, key, timings: dict | None = None):
         """InvSubBytes -> InvShiftRows -> InvMixColumns -> AddRoundKey(dk): one middle round of
         the equivalent inverse cipher (aes_tables.eq_inv_round), depth 7."""
-        import time
-        t0 = time.perf_counter()
+        t = time.perf_counter()
         Tb = self.inv_sub_bytes_shift_rows_mix(bits)
-        if timings is not None:
-            self.e.materialize(Tb)
-            self.e.synchronize()
-            t1 = time.perf_counter()
-            timings["inv_sub_bytes_shift_rows_mix"] = timings.get("inv_sub_bytes_shift_rows_mix", 0.0) + t1 - t0
+        t = self._mark(timings, "inv_sub_bytes_shift_rows_mix", t, Tb)
         out = self.inv_mix_columns_add_round_key(Tb, key)
-        if timings is not None:
-            self.e.materialize(out)
-            self.e.synchronize()
-            timings["inv_mix_columns_add_round_key"] = (timings.get("inv_mix_columns_add_round_key", 0.0)
-                                                        + time.perf_counter() - t1)
+        self._mark(timings, "inv_mix_columns_add_round_key", t, out)
         return out
 
     def final_round(self, bits, key):
@@ -1104,13 +1104,13 @@ class AESSlicedDecrypt(AESSlicedRound):
         (at key_levels): encrypt_aes128's body under this class's rounds; arguments as there."""
         return self.encrypt_aes128(bits, dkeys, bs, **kw)
 
-    def _check_cipher_input(self, data, dkeys, bss, want_levels, what: str):
+    def _check_cipher_input(self, data, dkeys, want_levels, what: str):
         """The refusals of transcipher_ecb / transcipher_cbc, before any ciphertext work."""
         shape = tuple(getattr(data, "shape", ()))
         if len(shape) != 3 or shape[0] < 1 or shape[1:] != (self.n_blk, 16):
             raise ValueError(f"data must be (NB, {self.n_blk}, 16) bytes, got {shape}")
-        if len(dkeys) != 11:
-            raise ValueError(f"expected 11 decryption keys, got {len(dkeys)}")
+        if len(dkeys) != self.ROUNDS + 1:
+            raise ValueError(f"expected {self.ROUNDS + 1} decryption keys, got {len(dkeys)}")
         have = [k[0][0].level for k in dkeys]
         if have != want_levels:
             raise ValueError(f"decryption keys at levels {have}; {what} needs {want_levels}")
@@ -1119,15 +1119,14 @@ class AESSlicedDecrypt(AESSlicedRound):
         """AES-128-ECB decryption of `data` ((NB, n_blk, 16) bytes) under the encrypted decryption
         keys, which sit at key_levels(L, bs, out_level), L = dkeys[0]'s level: the +-1 bit
         ciphertexts of the message and the number of refreshes.  State 0 = dk_0 times the data
-        planes (no encrypted input state, as counter_state), then rounds 1..10.  A wrong data
+        planes (no encrypted input state, as counter_state), then cipher_rounds.  A wrong data
         shape, keys at other levels and an out_level no bootstrapper can leave are ValueErrors
         before any ciphertext work."""
-        bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
         L = dkeys[0][0][0].level
-        want = self.key_levels(L, bss, out_level)  # ValueError: no bootstrapper leaves out_level
-        self._check_cipher_input(data, dkeys, bss, want, f"key_levels({L}, bs, out_level={out_level})")
+        want = self.key_levels(L, bs, out_level)  # ValueError: no bootstrapper leaves out_level
+        self._check_cipher_input(data, dkeys, want, f"key_levels({L}, bs, out_level={out_level})")
         S = self.mul_planes(dkeys[0], self.data_planes(data))
-        return self.rounds_1_to_10(S, dkeys, bss, out_level=out_level, **kw)
+        return self.cipher_rounds(S, dkeys, bs, out_level=out_level, **kw)
 
     def previous_blocks(self, data, iv):
         """The block before every block of `data` (aes_tables.cbc_previous): numpy on the oracle,
@@ -1153,12 +1152,11 @@ class AESSlicedDecrypt(AESSlicedRound):
         a rank's slice: the ciphertext block before its first).  The shifted ciphertext is folded
         into the last key (fold_data_key), so the chaining XOR costs the state no level; the keys
         sit at ctr_key_levels(L, bs, out_level).  Refusals and the result as transcipher_ecb."""
-        bss = list(bs) if isinstance(bs, (list, tuple)) else [bs]
         L = dkeys[0][0][0].level
-        want = self.ctr_key_levels(L, bss, out_level)
-        self._check_cipher_input(data, dkeys, bss, want, f"ctr_key_levels({L}, bs, out_level={out_level})")
+        want = self.ctr_key_levels(L, bs, out_level)
+        self._check_cipher_input(data, dkeys, want, f"ctr_key_levels({L}, bs, out_level={out_level})")
         prev = self.previous_blocks(data, iv)
         keys = list(dkeys)
-        keys[10] = self.fold_data_key(keys[10], prev)
+        keys[self.ROUNDS] = self.fold_data_key(keys[self.ROUNDS], prev)
         S = self.mul_planes(keys[0], self.data_planes(data))
-        return self.rounds_1_to_10(S, keys, bss, out_level=out_level, **kw)
+        return self.cipher_rounds(S, keys, bs, out_level=out_level, **kw)

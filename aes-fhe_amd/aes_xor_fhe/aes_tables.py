@@ -61,6 +61,7 @@ GF2 = GF_MUL_TABLES[2]
 GF3 = GF_MUL_TABLES[3]
 
 RCON = [0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36]
+ROUNDS = 10  # AES-128: ROUNDS + 1 round keys, the last round without MixColumns
 
 
 # ---------------------------------------------------------------------------------------------
@@ -107,22 +108,22 @@ def expand_key(key: bytes | np.ndarray) -> np.ndarray:
     key_expansion.py is empty; the harness does this step in plaintext)."""
     k = np.asarray(bytearray(key) if isinstance(key, (bytes, bytearray)) else key, dtype=np.uint8)
     w = [list(k[4 * i:4 * i + 4]) for i in range(4)]
-    for i in range(4, 44):
+    for i in range(4, 4 * (ROUNDS + 1)):
         t = list(w[i - 1])
         if i % 4 == 0:
             t = t[1:] + t[:1]
             t = [int(SBOX[b]) for b in t]
             t[0] ^= RCON[i // 4 - 1]
         w.append([w[i - 4][j] ^ t[j] for j in range(4)])
-    return np.array([sum(w[4 * r:4 * r + 4], []) for r in range(11)], dtype=np.uint8)
+    return np.array([sum(w[4 * r:4 * r + 4], []) for r in range(ROUNDS + 1)], dtype=np.uint8)
 
 
-def encrypt_block(block: np.ndarray, key: bytes | np.ndarray, rounds: int = 10) -> np.ndarray:
+def encrypt_block(block: np.ndarray, key: bytes | np.ndarray, rounds: int = ROUNDS) -> np.ndarray:
     rk = expand_key(key)
     s = np.asarray(block, dtype=np.uint8) ^ rk[0]
     for r in range(1, rounds + 1):
         s = shift_rows(sub_bytes(s))
-        if r != 10:
+        if r != ROUNDS:
             s = mix_columns(s)
         s = s ^ rk[r]
     return s
@@ -167,8 +168,8 @@ def decrypt_block(block: np.ndarray, key: bytes | np.ndarray) -> np.ndarray:
     """The straight inverse cipher (FIPS-197 5.3): the encryption round keys in reverse order,
     InvShiftRows -> InvSubBytes -> AddRoundKey -> InvMixColumns."""
     rk = expand_key(key)
-    s = np.asarray(block, dtype=np.uint8) ^ rk[10]
-    for r in range(9, 0, -1):
+    s = np.asarray(block, dtype=np.uint8) ^ rk[ROUNDS]
+    for r in range(ROUNDS - 1, 0, -1):
         s = inv_mix_columns(inv_sub_bytes(inv_shift_rows(s)) ^ rk[r])
     return inv_sub_bytes(inv_shift_rows(s)) ^ rk[0]
 
@@ -178,7 +179,7 @@ def decryption_keys(key: bytes | np.ndarray) -> np.ndarray:
     dk[i] = InvMixColumns(k_{10-i}) for i = 1..9, dk[10] = k_0."""
     rk = expand_key(key)
     dk = rk[::-1].copy()
-    dk[1:10] = inv_mix_columns(dk[1:10])
+    dk[1:ROUNDS] = inv_mix_columns(dk[1:ROUNDS])
     return dk
 
 
@@ -192,9 +193,9 @@ def eq_decrypt_block(block: np.ndarray, dk: np.ndarray) -> np.ndarray:
     """The equivalent inverse cipher under dk = decryption_keys(key): the structure of
     encrypt_block (an initial AddRoundKey, nine middle rounds, a last one without the mixing)."""
     s = np.asarray(block, dtype=np.uint8) ^ dk[0]
-    for r in range(1, 10):
+    for r in range(1, ROUNDS):
         s = eq_inv_round(s, dk[r])
-    return inv_shift_rows(inv_sub_bytes(s)) ^ dk[10]
+    return inv_shift_rows(inv_sub_bytes(s)) ^ dk[ROUNDS]
 
 
 def ecb_encrypt(data: np.ndarray, key: bytes | np.ndarray) -> np.ndarray:
@@ -244,12 +245,12 @@ def _encrypt_chain(blocks: list, rk: list, prev: int) -> list:
     out = []
     for p in blocks:
         s = p ^ prev ^ rk[0]
-        for rnd in range(1, 10):
+        for rnd in range(1, ROUNDS):
             t = rk[rnd]
             for i in range(16):
                 t ^= mid[i][(s >> shifts[i]) & 0xFF]
             s = t
-        t = rk[10]
+        t = rk[ROUNDS]
         for i in range(16):
             t ^= last[i][(s >> shifts[i]) & 0xFF]
         out.append(t)

@@ -211,22 +211,21 @@ def test_bits_fit_error_at_the_evaluated_points():
 
 
 def test_refresh_schedule():
-    """AESRowRound.needs_refresh: ten rounds on three refreshes at L = 30 (bootstrap output 19)
-    and at config 5's L = 35 (output 24); at most 2 middle rounds after a refresh."""
+    """AESRowRound.schedule: ten rounds on three refreshes at L = 30 (bootstrap output 19) and at
+    config 5's L = 35 (output 24); at most 2 middle rounds after a refresh."""
+    from types import SimpleNamespace as NS
     from aes_xor_fhe.aes_round_bits import AESRowRound
     R = AESRowRound.__new__(AESRowRound)
     for L, out in ((30, 19), (35, 24)):
-        lvl, since, nref, plan = L - 1, 0, 0, []
-        for rnd in range(1, 11):
+        plan = []
+        for rnd, lvl, b in R.schedule(L, NS(bits_level=out, stc_bits=[0] * 3)):
             final = rnd == 10
-            if R.needs_refresh(lvl, final, since, nref > 0, 3):
-                lvl, since, nref = out, 0, nref + 1
+            if b is not None:
+                assert lvl == out
                 plan.append("R")
-            lvl -= R.FINAL_DEPTH if final else R.ROUND_DEPTH
-            assert lvl >= 0
-            since += 1
+            assert lvl - (R.FINAL_DEPTH if final else R.ROUND_DEPTH) >= 0
             plan.append(str(rnd))
-        assert nref == 3, (L, plan)
+        assert plan.count("R") == 3, (L, plan)
         segs = "".join(plan).split("R")
         assert all(len([ch for ch in seg if ch != "0"]) <= 3 for seg in segs)
 
@@ -238,23 +237,23 @@ def test_pick_bootstrapper():
     cleaned (CLEAN_LEVELS) before the last refresh -- and the one before rounds 8-10 (7 + 7 + 5);
     at L = 35 the cheaper one serves all three and leaves room to clean as well."""
     from types import SimpleNamespace as NS
-    from aes_xor_fhe.aes_round_bits import AESRowRound
+    from aes_xor_fhe.aes_round_bits import AESRowRound, _Levels
     R = AESRowRound.__new__(AESRowRound)
+
+    class Logged(_Levels):  # the level-only state of the round loop, noting every refresh
+        def refresh(self, rnd, b, clean):
+            got.append(b.bits_level)
+            cleans.append(clean)
+            assert b is R.pick_bootstrapper(bss, rnd)
+            super().refresh(rnd, b, clean)
+
     for L, want in ((30, [17, 19, 19]), (35, [22, 22, 22])):
         bss = [NS(bits_level=L - 13, stc_bits=[0] * 3), NS(bits_level=L - 11, stc_bits=[0] * 3)]
-        lvl, since, got, cleans = L - 1, 0, [], []
-        for rnd in range(1, 11):
-            final = rnd == 10
-            if R.needs_refresh(lvl, final, since, bool(got), 3):
-                b = R.pick_bootstrapper(bss, rnd)
-                last = R.refreshes_after(rnd, b.bits_level, L - 11, 3) == 0
-                cleans.append(last and R.can_clean(lvl, since, bool(got), 3))
-                got.append(b.bits_level)
-                lvl, since = b.bits_level, 0
-            lvl -= R.FINAL_DEPTH if final else R.ROUND_DEPTH
-            assert lvl >= 0
-            since += 1
-        assert got == want, (L, got)
+        got, cleans = [], []
+        plan = R.run_rounds(Logged(R, L - 1), bss)
+        assert plan == R.schedule(L, bss) and len(plan) == 10
+        assert all(lvl - (R.FINAL_DEPTH if rnd == 10 else R.ROUND_DEPTH) >= 0 for rnd, lvl, _ in plan)
+        assert got == want == [b.bits_level for _, _, b in plan if b is not None], (L, got)
         assert cleans == [False, False, True], (L, cleans)  # the last refresh's input is cleaned
     # a single bootstrapper is always taken
     assert R.pick_bootstrapper(bss[1:], 8) is bss[1]

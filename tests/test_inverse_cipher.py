@@ -254,8 +254,8 @@ def test_transcipher_cbc_ten_rounds_oracle(oracle_lib):
 
 def test_transcipher_ecb_reduced_oracle(oracle_lib, monkeypatch):
     """transcipher_ecb's own code -- the checks, state 0 from the data planes, the hand-over to
-    rounds_1_to_10 with the keys at key_levels -- on a cipher reduced to rounds 1 and 10 (the
-    whole ten rounds run in the CBC test above, through the same rounds_1_to_10)."""
+    cipher_rounds with the keys at key_levels -- on a cipher reduced to rounds 1 and 10 (the
+    whole ten rounds run in the CBC test above, through the same cipher_rounds)."""
     e = Engine(log_n=10, max_level=13, seed=4, _lib=oracle_lib, special_primes=8)
     sk = e.create_secret_key(3)
     R = AESSlicedDecrypt(e, sk, e.create_public_key(sk), e.create_relinearization_key(sk))
@@ -271,7 +271,7 @@ def test_transcipher_ecb_reduced_oracle(oracle_lib, monkeypatch):
         seen["levels"] = {c.level for row in S for c in row}
         seen["kw"] = kw
         return R.final_round(R.round(S, keys[1]), keys[10]), 0
-    monkeypatch.setattr(R, "rounds_1_to_10", two_rounds)
+    monkeypatch.setattr(R, "cipher_rounds", two_rounds)
     levels = [L, L - 1 - 4] + [0] * 8 + [L - 1 - 7 - 4]
     monkeypatch.setattr(R, "key_levels", lambda *a, **k: levels)
     keys = [R.encrypt_round_key(k, level=v) for k, v in zip(dk, levels)]
